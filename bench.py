@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Benchmark of the material_mode=neural hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one scene through the U-Net stage of the hot path: SegmentationUNet + RegressionUNet
 forward on a device-resident 128^3 x 64 feature grid (BASELINE.json configs[1]) + argmax/one-hot
 combine, and (N > 1) the all-gather of the compact fields.  `value` = voxels/s over all ranks
-(weak scaling: one scene per rank per step).  The MPM half of the metric (BASELINE configs[2]:
-100k particles, n_grid 50) is timed in the same run and reported under "mpm" with its own roofline.
+(weak scaling: one scene per rank per step), `ms_per_step` = one timed step.  A plain run times that
+step alone; --full adds every other leg: the step's roofline, the MPM half of the metric (BASELINE
+configs[2]: 100k particles, n_grid 50, reported under "mpm" with its own roofline), the larger and
+plastic scenes, the pipeline, the CPU baselines.
 Synthetic data and seeded random-init weights (no datasets/checkpoints exist offline).
 Prints ONE JSON line on rank 0.
 """
@@ -122,9 +124,13 @@ def parse():
     ap.add_argument("--mpm-substeps", type=int, default=1000)
     ap.add_argument("--mpm-large-substeps", type=int, default=2000, help="substeps of the 1M-particle leg (BASELINE configs[4]: 2k)")
     ap.add_argument("--full", action="store_true",
-                    help="every leg.  Default: headline U-Net (+ its strict-fp32 twin), MPM 100 k (+ floor, 3-scene batch), MPM 1 M (+ two scenes), the "
-                         "reference's sand configuration at 1 M, the configs[2] pipeline, the CPU baselines.  --full adds: the other scatter mode at both "
-                         "sizes, the 1 M scene in motion, snow / metal / mixed at 1 M, six scenes per GPU, the 64^3 x 768 shipped shape, U-Net 256^3 x 128")
+                    help="every leg.  Default: the headline U-Net step alone (set-up, warm-up, the timed steps, the result line).  --full adds: the "
+                         "step's roofline and decomposition, its strict-fp32 twin, MPM 100 k (+ floor, 3-scene batch, the other scatter mode), MPM 1 M "
+                         "(+ two scenes, the other scatter mode, the scene in motion), the reference's sand / snow / metal / mixed configurations at 1 M, "
+                         "six scenes per GPU, field transfer, the configs[2] pipeline, the 64^3 x 768 shipped shape, U-Net 256^3 x 128, the CPU "
+                         "baselines, and the detail record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, < 64 MB: see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-small", action="store_true", help="time the U-Net CPU baseline at 64^3 instead of the headline grid (saves ~1 min)")
     ap.add_argument("--no-mpm", action="store_true")
@@ -148,7 +154,10 @@ def parse():
     ap.add_argument("--conv-precision", choices=["f16x3", "f32"], default=None,
                     help="f16x3 (default): fp32 operands split into fp16 hi+lo, 3 f16 MFMAs per product, fp32 accumulate; "
                          "f32: exact-fp32 MFMA everywhere")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def barrier_sync(world):
@@ -263,7 +272,25 @@ class ConvProfiler:
         return agg
 
 
-def bench_unet(args, rank, world, device, precision_override=None, steps=None, warmup=None, device_input=False):
+DUMP_BYTES = 60_000_000
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: what one step of the timed path hands its caller -- predict_material_field's (combined, seg_pred, seg_logits,
+    cont_pred) -- as <name>.npy in float32, one row per channel.  The four arrays hold the same voxels: a fixed sample (seed 0, in
+    ascending order) sized to keep the set under DUMP_BYTES, or the whole grid where it fits (23 floats per voxel: ~0.65 M of the
+    2.1 M voxels of a 128^3 grid).  With the same arguments the inputs are the same, so two builds compare output for output."""
+    import numpy as np
+    n_vox = outputs[1][0].numel()
+    rows = [t.reshape(-1, n_vox) for t in outputs]
+    n = min(n_vox, DUMP_BYTES // (4 * sum(r.shape[0] for r in rows)))
+    idx = torch.randperm(n_vox, generator=torch.Generator().manual_seed(0))[:n].sort().values.to(rows[0].device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, r in zip(("combined", "seg_pred", "seg_logits", "cont_pred"), rows):
+        np.save(os.path.join(out_dir, name + ".npy"), r.index_select(1, idx).float().cpu().numpy())
+
+
+def bench_unet(args, rank, world, device, precision_override=None, steps=None, warmup=None, device_input=False, dump_dir=None):
     from pixie_amd.unet import RegressionUNet, SegmentationUNet, predict_material_field
     D, C = args.grid, args.feature_channels
     n_steps = args.steps if steps is None else steps
@@ -284,10 +311,10 @@ def bench_unet(args, rank, world, device, precision_override=None, steps=None, w
         feat = torch.from_numpy(feature_grid(D, C, seed=100 + rank)).to(device)  # scene i uses seed 100+i
 
     def step(dual_stream=None):
-        combined, seg_pred, _, cont_pred = predict_material_field(seg, cont, feat, dual_stream=dual_stream)
+        out = predict_material_field(seg, cont, feat, dual_stream=dual_stream)    # (combined, seg_pred, seg_logits, cont_pred)
         if world > 1:
-            pd.all_gather_fields(cont_pred, seg_pred)
-        return combined
+            pd.all_gather_fields(out[3], out[1])
+        return out
 
     for _ in range(3):   # set-up, not warm-up steps: pack the weights, take the normalisation bounds, record the HIP graphs, and
         step()           # replay them twice (the first replays of a freshly instantiated graph run ~8 % slower: 90 vs 84 ms)
@@ -296,13 +323,22 @@ def bench_unet(args, rank, world, device, precision_override=None, steps=None, w
     executor = f"{seg.executor}{'+hip_graph' if seg.use_graph else ''}"
     tele0 = gpu_telemetry(device.index or 0)
     tele_mid = {}
+    last = []
 
     def step_and_sample(_n=[0]):
-        step()
+        out = step()
         _n[0] += 1
         if _n[0] == n_steps:
+            last.append(out)
             tele_mid.update(gpu_telemetry(device.index or 0))    # while the last steps are still running on the device
     dt = timed_steps(step_and_sample, n_steps, world, device)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last[0])
+    flops_scene = conv_flops(seg.cfg) + conv_flops(cont.cfg)
+    if not args.full:    # a plain run: the headline step alone
+        return dict(seconds=dt, steps=n_steps, voxels=world * n_steps * D ** 3, flops_scene=flops_scene, roofline=None, precision=precision,
+                    executor=executor, conv_ms_per_step=None, layer_ms={}, kernel_avg={}, kernel_avg_timed=None,
+                    step_parts={"telemetry_before": tele0, "telemetry_during": tele_mid}, allgather_ms=None)
     ag_ms = None
     if world > 1:
         _, sp_, _, cp_ = predict_material_field(seg, cont, feat)
@@ -357,7 +393,6 @@ def bench_unet(args, rank, world, device, precision_override=None, steps=None, w
         print(f"bench.py: H2D timing failed: {exc}", file=sys.stderr)
     parts["telemetry_before"] = tele0
     parts["telemetry_during"] = tele_mid
-    flops_scene = conv_flops(seg.cfg) + conv_flops(cont.cfg)
     # dominant kernel: the full-resolution 64->64 3x3x3 conv (82 % of FLOPs are at full resolution).  The timed region above is
     # the product default: each network is ONE pixie_unet_forward call replayed as a captured HIP graph, the two networks back
     # to back on one stream -- no per-launch events can be placed inside a replay.  The launch durations the roofline is computed
@@ -948,8 +983,10 @@ def main():
     # record keeps one tail window for both streams), anything else a library prints goes to stderr
     import pixie_amd.mpm_solver as _shim
     _shim.VERBOSE = False
+    if not args.full:    # a plain run: the headline step alone (bench_unet skips its diagnostics); every other leg is --full's
+        args.no_exact_f32 = args.no_mpm = args.no_cpu_baseline = True
     with contextlib.redirect_stdout(sys.stderr):
-        u = U(args, rank, world, device)
+        u = U(args, rank, world, device, dump_dir=args.dump_outputs)
         # the same step on the exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32, no operand splitting): the precision ruling
         # of VERDICT r1 asks for this line beside the headline; a few steps suffice (bounded run time)
         u32 = None
@@ -1025,7 +1062,9 @@ def main():
             if rank == 0 and world == 1 and not args.no_cpu_baseline:
                 cpu = cpu_baselines(args)
 
-    if rank == 0:
+    if rank == 0 and not args.full:    # (no detail record: everything in it beyond the line comes from --full's legs)
+        print(json.dumps(compact_line(assemble_detail(args, world, u, threads_per_rank=threads, dry=dry))))
+    elif rank == 0:
         detail = assemble_detail(args, world, u, u32, m, m_large, m_alt, m_large_alt, m_multi, ft, shipped, u256, cpu,
                                  threads_per_rank=threads, dry=dry)
         if pipe is not None:

@@ -9,7 +9,7 @@ UNMODIFIED on tests/golden/ti_shim (a NumPy interpreter of the Taichi subset it 
 get_particle_volume / init_filled_particles are run as written on five scenes (tests/golden/make_filling_ref_golden.py ->
 tests/golden/filling_ref_golden.npz).  This restatement reproduces the reference's density grids to 4e-16, its count grids
 after each of the three kernels, the filled cells, the volumes and the nearest-Gaussian attributes exactly
-(tests/test_filling_ref_golden.py, which also re-runs the reference live where /root/reference exists).  Not pinnable, because
+(tests/test_filling_ref_golden.py, with one more small scene in tests/golden/filling_ref_small.npz).  Not pinnable, because
 the reference itself leaves them undetermined: the order of the new particles and their ti.random() offsets.  The closed-form
 and brute-force anchors of tests/test_filling_oracle.py stay as a second, independent check.  The smoothing step at the end
 of this file (PyMCubes, absent) is the one part that remains unpinned; see its docstring.

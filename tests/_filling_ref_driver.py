@@ -40,6 +40,14 @@ def _torus(n, seed, R, r, sigma):
     return pos.astype(np.float32), np.full(n, 0.9, np.float32), cov.astype(np.float32)
 
 
+def small_scene():
+    """The 12^3 scene of tests/golden/filling_ref_small.npz (tests/test_filling_ref_golden.py::test_live_reference_run_small_scene)."""
+    n, dx = 12, 1.0 / 12
+    p, o, c = _shell(500, 9, (0.5, 0.5, 0.5), (0.38, 0.38, 0.38), (0.4 * dx, 0.55 * dx))
+    kw = dict(density_thres=1.0, search_thres=0.6, max_particles_per_cell=2, search_exclude_dir=5, ray_cast_dir=4)
+    return dict(pos=p, opacity=o, cov=c, grid_n=n, grid_dx=dx, kw=kw)
+
+
 def scenes():
     """name -> dict(pos, opacity, cov, grid_n, grid_dx, and the keyword arguments of fill_particles)."""
     n = 24

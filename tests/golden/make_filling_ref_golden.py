@@ -18,6 +18,7 @@ Every threshold is checked to be >= 2e-4 (relative) away from every cell's densi
 integer results, so no comparison against this fixture hinges on a rounding.
 
 Run in the build container (needs /root/reference):   python tests/golden/make_filling_ref_golden.py      (~8 min)
+`... make_filling_ref_golden.py small` writes only filling_ref_small.npz: the grids of _filling_ref_driver.small_scene() (seconds).
 """
 import json
 import os
@@ -84,5 +85,14 @@ def main():
     print("wrote", path, os.path.getsize(path) // 1024, "KB")
 
 
+def small():
+    mod, ti = drv.load_reference()
+    assert mod.__file__.startswith("/root/reference/"), mod.__file__
+    r = drv.run_reference(mod, ti, drv.small_scene(), "f64", seed=3)
+    path = os.path.join(HERE, "filling_ref_small.npz")
+    np.savez_compressed(path, density=r["density"], **{k: r[k] for k in INT_KEYS})
+    print("wrote", path, os.path.getsize(path) // 1024, "KB")
+
+
 if __name__ == "__main__":
-    main()
+    small() if sys.argv[1:] == ["small"] else main()

@@ -17,6 +17,7 @@ of its particles with det F < 0 and is stored under both conventions (`inverted`
 show what depends on the convention and that the oracle follows Warp's.
 
 Run in the build container (needs /root/reference):   python tests/golden/make_mpm_ref_golden.py      (~2 min)
+`--check` re-computes one scene and compares it with the committed fixture instead of writing one.
 
 `--long` writes tests/golden/mpm_ref_long_golden.npz instead: two ROLLOUTS of 150 substeps by the same reference code (the tree
 scenario of PhysGaussian/config/objaverse/custom_tree_config.json on a ball with per-particle E / nu / density, and a sand
@@ -274,5 +275,15 @@ def main():
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def check():
+    """--check: re-computes jelly_rpic with the reference's code and compares it with the committed fixture (exit 1 on any difference)."""
+    sc, arr = scenes()["jelly_rpic"]
+    snaps, _, _ = rollout(sc, arr, "f64")
+    z = np.load(os.path.join(HERE, "mpm_ref_golden.npz"))
+    err = max(float(np.abs(snaps[cp][f] - z[f"jelly_rpic/k{cp}/{f}"]).max()) for cp in sc["checkpoints"] for f in STATE_FIELDS)
+    print("LIVE_MAX_ABS_DIFF", err)
+    sys.exit(0 if err == 0.0 else 1)
+
+
 if __name__ == "__main__":
-    main()
+    check() if "--check" in sys.argv else main()

@@ -42,6 +42,10 @@ CASES = {
                         attention_resolutions=(), grid_size=8), 5, 6),
 }
 HEADS = (("seg", 8, 0), ("cont", 3, 1000))  # (name, out_channels, weight-seed offset)
+# one head of one more architecture -- two res blocks per level, attention at resolution 4, five output channels -- written to
+# unet_live8.npz for tests/test_unet_oracle.py::test_oracle_matches_reference_live: (cfg kwargs, out_channels, weight seed, input seed)
+LIVE8 = (dict(feature_channels=64, cond_dim=32, model_channels=32, num_res_blocks=2, channel_mult=(1, 2, 2),
+              attention_resolutions=(4,), grid_size=8), 5, 7, 11)
 
 
 def reference_model(cfg: UNetConfig) -> nn.Module:
@@ -91,6 +95,11 @@ def main():
             print(name, head, res[head].shape, float(np.abs(res[head]).mean()))
         np.savez_compressed(os.path.join(out_dir, f"unet_{name}.npz"), seg=res["seg"], cont=res["cont"],
                             weight_seed=wseed, input_seed=iseed)
+    if not only or "live8" in only:
+        kw, oc, wseed, iseed = LIVE8
+        out = run_reference(UNetConfig(out_channels=oc, **kw), wseed, feature_grid(kw["grid_size"], kw["feature_channels"], seed=iseed))
+        print("live8", out.shape, float(np.abs(out).mean()))
+        np.savez_compressed(os.path.join(out_dir, "unet_live8.npz"), out=out, weight_seed=wseed, input_seed=iseed)
 
 
 if __name__ == "__main__":

@@ -89,16 +89,11 @@ def test_oracle_reproduces_the_reference_volumes_and_attributes(name):
 
 
 def test_live_reference_run_small_scene():
-    """Re-computes a small scene with the reference's code where /root/reference exists (the build container)."""
-    try:
-        mod, ti = drv.load_reference()
-    except FileNotFoundError:
-        pytest.skip("needs /root/reference (build container only)")
-    n, dx = 12, 1.0 / 12
-    p, o, c = drv._shell(500, 9, (0.5, 0.5, 0.5), (0.38, 0.38, 0.38), (0.4 * dx, 0.55 * dx))
-    kw = dict(density_thres=1.0, search_thres=0.6, max_particles_per_cell=2, search_exclude_dir=5, ray_cast_dir=4)
-    sc = dict(pos=p, opacity=o, cov=c, grid_n=n, grid_dx=dx, kw=kw)
-    r = drv.run_reference(mod, ti, sc, "f64", seed=3)
+    """A small scene of its own (12^3, two particles per cell) against the grids the reference's code computed for it, stored by
+    tests/golden/make_filling_ref_golden.py small (filling_ref_small.npz)."""
+    r = np.load(os.path.join(os.path.dirname(__file__), "golden", "filling_ref_small.npz"))
+    sc = drv.small_scene()
+    p, o, c, n, dx, kw = sc["pos"], sc["opacity"], sc["cov"], sc["grid_n"], sc["grid_dx"], sc["kw"]
     count0, dens = fo.densify(p.astype(np.float64), o, c, n, np.float64(np.float32(dx)))
     assert np.array_equal(count0, r["count_after_densify_grids"])
     assert np.abs(dens - r["density"]).max() <= 1e-12 * dens.max()

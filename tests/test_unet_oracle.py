@@ -8,7 +8,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-from make_unet_golden import CASES, HEADS  # noqa: E402
+from make_unet_golden import CASES, HEADS, LIVE8  # noqa: E402
 
 from oracle import unet_oracle
 from pixie_amd.synthetic import feature_grid
@@ -17,7 +17,6 @@ from pixie_amd.unet_plan import UNetConfig, build_plan, conv_flops, param_shapes
 from tests._torch_ref_ops import TorchRefOps
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-REFERENCE = "/root/reference/third_party/Wavelet-Generation"
 
 
 def rel_l2(a, b):
@@ -39,16 +38,16 @@ def test_oracle_matches_reference_golden(name):
         assert np.abs(g[head]).mean() > 0.05  # golden is not the vacuous all-zero output of fresh weights
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
 def test_oracle_matches_reference_live():
-    from make_unet_golden import run_reference
-    kw = dict(feature_channels=64, cond_dim=32, model_channels=32, num_res_blocks=2, channel_mult=(1, 2, 2),
-              attention_resolutions=(4,), grid_size=8)
-    feat = feature_grid(8, 64, seed=11)
-    cfg = UNetConfig(out_channels=5, **kw)
-    ref = run_reference(cfg, 7, feat)  # load_state_dict(strict=True) inside also proves the key plan
-    y = unet_oracle.unet_forward(synthetic_state_dict(cfg, 7), cfg, feat).numpy()
-    assert rel_l2(y, ref) < 1e-6
+    """One more architecture (two res blocks per level, attention at resolution 4, five output channels) against the output
+    of the reference's own modules, stored by tests/golden/make_unet_golden.py (unet_live8.npz)."""
+    kw, oc, wseed, iseed = LIVE8
+    g = np.load(os.path.join(GOLDEN, "unet_live8.npz"))
+    cfg = UNetConfig(out_channels=oc, **kw)
+    y = unet_oracle.unet_forward(synthetic_state_dict(cfg, wseed), cfg, feature_grid(kw["grid_size"], kw["feature_channels"], seed=iseed)).numpy()
+    assert y.shape == g["out"].shape
+    assert rel_l2(y, g["out"]) < 1e-6
+    assert np.abs(g["out"]).mean() > 0.05
 
 
 def test_plan_structure_matches_survey_appendix():

@@ -121,6 +121,23 @@ int pixie_mpm_add_particle_modifier(pixie_mpm* h, const pixie_pmod_desc* pm, voi
 /* p2g2p (mpm_solver_warp.py:514-637), n_substeps times with the same dt; advances h->time. */
 int pixie_mpm_step(pixie_mpm* h, double dt, int n_substeps, void* stream);
 
+/* Several independent scenes stepped together (no reference counterpart): every substep of every scene in ONE block-kernel
+ * launch and ONE grid-kernel launch (one per kernel variant when the scenes differ in work-item capacity or scatter mode),
+ * instead of two launches per scene.
+ *   pixie_mpm_batch_create: 1 ... 32 distinct handles (kMaxBatch).  The batch owns its device tables and staging buffers, not
+ *     the scenes: every handle must outlive the batch.
+ *   pixie_mpm_batch_step: advances every scene by n_substeps substeps of dt on `stream`; each scene ends in exactly the bits
+ *     pixie_mpm_step(h, dt, n_substeps, stream) gives it alone.  Each handle's state is re-read at the start of every call, so
+ *     regrid / set_field / set_scalar / add_bc between calls are picked up.  n_substeps == 0 is a no-op.  Successive calls on
+ *     different streams must be ordered by the caller, as for pixie_mpm_step.
+ * Both refuse -- with a pixie_last_error message, before anything is launched or changed -- a null or repeated handle, an empty
+ * or too long list, a scene with a phase-API P2G pending, with `trace` set, with more than 16 boundary conditions or with more
+ * than 8 particle modifiers (the cases pixie_mpm_step serves with extra launches). */
+typedef struct pixie_mpm_batch pixie_mpm_batch;
+int pixie_mpm_batch_create(pixie_mpm_batch** out, pixie_mpm* const* handles, int n_handles);
+int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* stream);
+int pixie_mpm_batch_destroy(pixie_mpm_batch* b);
+
 /* compute_cov_from_F (mpm_utils.py:529-553) and compute_R_from_F (:556-580) as used by
  * export_particle_cov_to_torch / export_particle_R_to_torch (mpm_solver_warp.py:702-741). */
 int pixie_mpm_export_cov(pixie_mpm* h, float* d_cov /* [n][6] */, void* stream);

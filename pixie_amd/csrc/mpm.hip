@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
+#include <cstddef>
 #include <cstring>
 #include <map>
 #include <string>
@@ -657,175 +659,7 @@ __global__ __launch_bounds__(kWG, OCC) void mpm_block_kernel(MpmPtrs S, StepPara
         const int per = (int)gridDim.x >> 3;
         if (item < (per << 3)) item = (item & 7) * per + (item >> 3);      // (the last n % 8 items keep their place)
     }
-    const int4 it = S.items[item];
-    const int tid = threadIdx.x;
-    const int nthr = blockDim.x;   // = the work-item capacity of the current binning (256; 128 on request)
-    const int bz = it.x % S.nbk, by = (it.x / S.nbk) % S.nbk, bx = it.x / (S.nbk * S.nbk);
-    const int ox = bx * kBS - 1, oy = by * kBS - 1, oz = bz * kBS - 1;
-    const int ng = S.ng;
-    PX_MPM_STAMP(0);
-    Preload L;
-    L.selection = 1;
-    if (tid < it.z) preload_particle<DO_G2P, DO_P2G>(S, it.y + tid, L);   // in flight while the tile is staged
-    for (int idx = tid; idx < kTN; idx += nthr) {
-        if (DO_G2P) {
-            const int gz = oz + (idx & (kTS - 1)), gy = oy + ((idx >> 3) & (kTS - 1)), gx = ox + (idx >> 6);
-            float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)gx < (unsigned)ng && (unsigned)gy < (unsigned)ng && (unsigned)gz < (unsigned)ng && !(TRACE && (sp.trace & 0x400)))
-                g = S.gout[((size_t)gx * ng + gy) * ng + gz];
-            tv[idx] = g;
-        }
-        if (DO_P2G) {
-            ta[0][idx] = 0ull; ta[1][idx] = 0ull;
-            if (!PACK) { ta[2][idx] = 0ull; ta[3][idx] = 0ull; }
-        }
-    }
-    __syncthreads();
-    PX_MPM_STAMP(1);
-
-    // One chunk of <= 256 particles per work item.  Sharing one tile between more particles was measured both ways and
-    // loses: (a) a workgroup looping over several 256-particle chunks (integer sums folded into an fp32 tile between
-    // chunks) -- hipcc 7.2 keeps 176 VGPRs live across the loop (3 waves per SIMD instead of 5); (b) work items of 384 ...
-    // 1024 threads -- 107 ... 132 us per launch at 1 M particles against 81 us for 256 (r2g): every barrier then waits
-    // for the slowest of 6 ... 16 waves.  The per-item costs (staging, zeroing, publish) are the smaller evil.
-    const int q = tid;
-    ScatterIn in;
-    in.active = false;
-    if (q < it.z) particle_phase1<DO_G2P, DO_P2G, SCHED>(S, sp, pms, it.y + q, ox, oy, oz, tv, L, in);
-    if (!DO_P2G) return;
-    PX_MPM_STAMP(2);
-
-    // ---- P2G: a particle whose stencil left the tile goes straight to HBM (fp32 atomics into gin) ----
-    Stencil st;
-    int b0 = -1;
-    if (in.active) {
-        st = make_stencil(in.x[0], in.x[1], in.x[2], S.inv_dx);
-        if (!stencil_inside(st, ng)) {
-            atomicAdd(S.oob, 1ull);
-            S.selection[it.y + q] = 2;
-            Mat3 Fnow;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Fnow.m[i] = S.F[i * S.n + it.y + q];     // (the return-mapped F this launch has just stored)
-            freeze_particle_state(S, it.y + q, Fnow);
-            in.active = false;
-        } else {
-            const int lx = st.base[0] - ox, ly = st.base[1] - oy, lz = st.base[2] - oz;
-            if ((unsigned)lx <= (unsigned)(kTS - 3) && (unsigned)ly <= (unsigned)(kTS - 3) && (unsigned)lz <= (unsigned)(kTS - 3)) {
-                b0 = (lx * kTS + ly) * kTS + lz;
-            } else {
-                atomicAdd(S.oob + 1, 1ull);
-                float mvAT[21];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) mvAT[a] = in.mv[a];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) { mvAT[3 + k] = in.A.m[k]; mvAT[12 + k] = in.T.m[k]; }
-                if (!p2g_scatter_global(S.gin, S.blk_flags, S.nbk, ng, st, mvAT, in.mass)) atomicAdd(S.oob + 2, 1ull);
-                in.active = false;
-            }
-        }
-    }
-    // ---- workgroup bounds -> power-of-two scales ----
-    // One contribution of a particle is  w (mv_a + A_a . d) + T_a . g  with  w <= 0.75^3, |d_b| <= 1.5, |g_b| <= 0.75^2 (the
-    // B-spline weights and their derivatives in cell units), so  r_p = max_a [0.421875 (|mv_a| + 1.5 sum_b |A_ab|) +
-    // 0.5625 sum_b |T_ab|]  bounds every contribution of particle p.
-    //   exact mode: scale by the workgroup MAXIMUM of r_p to [2^41, 2^42): 256 contributions stay below 2^50.
-    //   packed mode: scale by the workgroup SUM of r_p to [2^29, 2^30): |any node sum| <= sum_p r_p < 2^30 whatever the
-    //     particle count, and the quantum is 2^-30 of the SUM instead of 2^-22 of 256 maxima -- typically 10-20x finer
-    //     (the sum of ~180 bounds of which most are well below the largest).  Same for the masses.
-    float bp = 0.0f, bm = 0.0f;
-    if (TRACE && (sp.trace & 0x200)) { bp = PACK ? 256.0f : 1.0f; bm = PACK ? 0.256f : 1e-3f; }
-    else {
-        if (in.active) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float r = 0.421875f * (fabsf(in.mv[a]) + 1.5f * (fabsf(in.A.m[3 * a]) + fabsf(in.A.m[3 * a + 1]) + fabsf(in.A.m[3 * a + 2]))) +
-                                0.5625f * (fabsf(in.T.m[3 * a]) + fabsf(in.T.m[3 * a + 1]) + fabsf(in.T.m[3 * a + 2]));
-                bp = fmaxf(bp, r);
-            }
-            bm = 0.421875f * in.mass;
-        }
-        if (PACK) { bp = wave_sum(bp); bm = wave_sum(bm); }
-        else { bp = wave_max_nonneg(bp); bm = wave_max_nonneg(bm); }
-        if ((tid & 63) == 0) { s_red[0][tid >> 6] = bp; s_red[1][tid >> 6] = bm; }
-        __syncthreads();
-        bp = s_red[0][0]; bm = s_red[1][0];
-        for (int w = 1; w < (nthr >> 6); ++w) {
-            if (PACK) { bp += s_red[0][w]; bm += s_red[1][w]; }     // (fixed order: the scale is reproducible)
-            else { bp = fmaxf(bp, s_red[0][w]); bm = fmaxf(bm, s_red[1][w]); }
-        }
-    }
-    constexpr int kTop = PACK ? 29 : 41;
-    const float sP = scale_for(bp, kTop), sM = scale_for(bm, kTop);
-    PX_MPM_STAMP(3);
-
-    if (in.active) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) in.mv[a] *= sP;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { in.A.m[k] *= sP; in.T.m[k] *= sP; }
-        p2g_scatter<SCHED>(st, in.mv, in.A, in.T, in.mass * sM, [&](int i, int j, int k, const float mom[3], float m) {
-            const int idx = b0 + (i * kTS + j) * kTS + k;
-            if (TRACE && (sp.trace & 0x100)) { asm volatile("" :: "v"(mom[0]), "v"(mom[1]), "v"(mom[2]), "v"(m)); return; }
-            if (PACK) {
-                // v_cvt_rpi rounds exact ties UP, and ties are common (a contribution of magnitude 2^22 is a float with one
-                // fractional bit): left alone that is a drift of ~0.2 quanta per contribution in +x, +y, +z -- measured as
-                // 3e-3 of the total momentum over 500 substeps.  Neighbouring nodes therefore alternate: (i + j + k) even
-                // adds round(x), odd SUBTRACTS round(-x), i.e. rounds ties down.  Unbiased, and still a pure function of
-                // the particle's own data (deterministic, order-independent).
-                if (((i + j + k) & 1) == 0) {
-                    atomicAdd(&ta[0][idx], pack_pair(round_to_int(mom[0]), round_to_int(mom[1])));
-                    // the mass is never negative: in the low half it needs no borrow correction
-                    atomicAdd(&ta[1][idx], (unsigned long long)(unsigned)round_to_int(m) | ((unsigned long long)(unsigned)round_to_int(mom[2]) << 32));
-                } else {
-                    __hip_atomic_fetch_sub(&ta[0][idx], pack_pair(round_to_int_neg(mom[0]), round_to_int_neg(mom[1])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_sub(&ta[1][idx], pack_pair(round_to_int_neg(m), round_to_int_neg(mom[2])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            } else {
-                atomicAdd(&ta[0][idx], to_fixed(mom[0]));
-                atomicAdd(&ta[1][idx], to_fixed(mom[1]));
-                atomicAdd(&ta[2][idx], to_fixed(mom[2]));
-                atomicAdd(&ta[3][idx], to_fixed(m));
-            }
-        });
-    }
-    // where this thread's nodes go in the staged tile: fetched now, consumed behind the barrier
-    const unsigned lut = (nthr == kWG) ? S.staged_lut[tid] : 0u;
-    __syncthreads();
-    PX_MPM_STAMP(4);
-    const float iP = pow2_reciprocal(sP), iM = pow2_reciprocal(sM);
-    // ---- publish the tile: coalesced stores; the grid update sums the tiles that cover each node ----
-    float4* dst = S.part + (size_t)item * kTN;
-    if (!(TRACE && (sp.trace & 0x800)))
-        for (int idx = tid; idx < kTN; idx += nthr) {
-            float4 o;
-            if (PACK) {
-                int px, py, pm, pz;
-                unpack_pair(ta[0][idx], px, py);
-                const unsigned long long w1 = ta[1][idx];
-                pm = (int)(unsigned)w1; pz = (int)(unsigned)(w1 >> 32);
-                o = make_float4((float)px * iP, (float)py * iP, (float)pz * iP, (float)pm * iM);
-            } else {
-                o = make_float4(from_fixed(ta[0][idx], iP), from_fixed(ta[1][idx], iP), from_fixed(ta[2][idx], iP), from_fixed(ta[3][idx], iM));
-            }
-            // (staged_index is ~30 instructions of selects per node; with the usual 256-thread work items each thread's two
-            // nodes are tid and tid + 256 and their staged positions come from a 1 KB table, two 16-bit halves of one word)
-            const int si = (nthr == kWG) ? (int)((idx < kWG) ? (lut & 0xffffu) : (lut >> 16)) : staged_index(idx >> 6, (idx >> 3) & 7, idx & 7);
-            // Typically 40-60 % of a tile's nodes received nothing (the drift margin planes, corners beyond every stencil): they
-            // are neither stored nor -- by the mask -- read back.  Adding an all-zero float4 is a no-op, so the sums are unchanged.
-            const bool nz = (o.x != 0.0f) | (o.y != 0.0f) | (o.z != 0.0f) | (o.w != 0.0f);
-            if (S.sparse_tiles) {
-                const unsigned long long live = __ballot(nz);     // lanes of a wave hold 64 consecutive nodes
-                if ((tid & 63) == 0) S.tile_mask[(size_t)item * 8 + (idx >> 6)] = live;
-                if (nz) dst[si] = o;
-            } else {
-                dst[si] = o;
-            }
-        }
-    PX_MPM_STAMP(5);
-#ifdef PIXIE_DIAG
-    if (TRACE && (sp.trace & 1) && tid == 0 && blockIdx.x < (unsigned)kMpmTraceItems)   // where it ran: HW_ID | XCC_ID << 32
-        g_mpm_trace[blockIdx.x * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
-#endif
+#include "mpm_block_body.h"
 }
 
 // ------------------------------------------------------------------ re-binning (counting sort by block)
@@ -1352,6 +1186,92 @@ __global__ __launch_bounds__(64) void mpm_grid_block_kernel(MpmPtrs S, StepParam
     S.gout[((size_t)ix * S.ng + iy) * S.ng + iz] = finish_node(S, sp, bcs, make_float4(0.f, 0.f, 0.f, 0.f), ix, iy, iz);
 }
 
+// ------------------------------------------------------------------ several scenes per launch (pixie_mpm_batch_*)
+// A 100 k-particle scene gives one launch ~500 work items and ~2000 active blocks: too little to fill the chip, and each scene pays
+// its own two launches per substep.  The batched wrappers put the work items of up to kMaxBatch scenes into ONE block-kernel launch
+// and their active blocks into ONE grid-kernel launch, then run the solo kernels' own bodies on them.
+//
+// Where the per-scene parameters come from (kernel arguments would be ~2 KB per scene, and a copy per launch costs about what the
+// launch saves):
+//   * BatchScene, one per scene, in device memory: the scene's MpmPtrs, ALL its registered modifiers (impulses first -- the order of
+//     active_pmods; apply_pmod re-checks each window with the same float compare, so applying the inactive ones is a no-op), and
+//     pointers into this call's tables.  Written at the start of each pixie_mpm_batch_step and again after a re-binning of the scene
+//     (rebin() has just synchronised the stream: nothing in flight reads the old descriptor).
+//   * this call's tables, precomputed on the host at the start of the call and uploaded with the descriptors in ONE copy: the
+//     StepParams of every substep (only `time` advances) and the BCSet of every grid launch (moving cuboids advance in double on the
+//     host and are stored as float, advance_bcs_state) -- one BCSet for the whole call when the scene has no cuboid.
+//   * BatchLaunch, the kernel argument (~270 bytes): which scenes this launch covers and the prefix of their work items (or active
+//     blocks).  Everything that changes at a re-binning of one scene -- item counts, the capacity that groups launches -- is here.
+// The descriptor is read through an address-space-4 (constant) pointer with a wave-uniform scene index: scalar loads, as the solo
+// kernels' parameters are.  The block kernel copies MpmPtrs and StepParams into locals at entry: read through references the same
+// body was scheduled differently from the solo kernel and contracted other multiply-adds (F_trial differed in the last bit).
+constexpr int kMaxBatch = 32;
+struct BatchScene {
+    MpmPtrs S;
+    PModSet pms;                   // every registered modifier, impulses first
+    const StepParams* sp;          // [n_substeps + 1] of this call: the launch of `step` reads sp[step]
+    const unsigned char* bcs;      // BCSet records of this call's grid launches: grid launch `step` reads bcs + step * bc_stride
+    long long bc_stride;           // 0: no cuboid -- one record for the whole call
+};
+struct BatchLaunch {
+    const BatchScene* scenes;      // device descriptors
+    int n;                         // scenes in this launch
+    int step;                      // substep index into the call's tables
+    int xcd_order;                 // work items dealt to the XCDs in contiguous runs (as mpm_block_kernel)
+    int pad;
+    int scene[kMaxBatch];          // descriptor of launch scene k
+    int first[kMaxBatch + 1];      // first global work item (block kernel) / active block (grid kernel) of launch scene k
+};
+typedef const BatchScene __attribute__((address_space(4))) ConstBatchScene;
+
+// launch scene of global index `g` (wave-uniform: g is a workgroup index), and the descriptor it reads
+__device__ __forceinline__ int batch_scene_of(const BatchLaunch& L, int g) {
+    int k = 0;
+    for (int j = 1; j < L.n; ++j) k += (g >= L.first[j]) ? 1 : 0;
+    return __builtin_amdgcn_readfirstlane(k);
+}
+// what a descriptor points at (this call's tables) is read the same way: through a constant-address-space view of the pointer
+template <class T>
+__device__ __forceinline__ const T& const_view(const T* p) {
+    return *(const T*)(const T __attribute__((address_space(4)))*)p;
+}
+__device__ __forceinline__ const BatchScene& batch_desc(const BatchLaunch& L, int k) {
+    const ConstBatchScene* d = (const ConstBatchScene*)L.scenes + L.scene[k];
+    return *(const BatchScene*)d;
+}
+
+template <bool DO_G2P, bool DO_P2G, int OCC, int FL>
+__global__ __launch_bounds__(kWG, OCC) void mpm_block_batch_kernel(BatchLaunch BL) {
+    constexpr bool PACK = (FL & F_PACK32) != 0;     // (the prologue of mpm_block_kernel)
+    constexpr bool TRACE = (FL & F_TRACE) != 0;
+    constexpr bool SCHED = (FL & F_WIDE) == 0;
+    __shared__ float4 tv[kTN];
+    __shared__ unsigned long long ta[PACK ? 2 : 4][kTN];
+    __shared__ float s_red[2][kWG / 64];
+    // global work item (remapped over the XCDs like mpm_block_kernel's) -> (scene, the scene's own work item)
+    int item = (int)blockIdx.x;
+    if (BL.xcd_order) {
+        const int per = (int)gridDim.x >> 3;
+        if (item < (per << 3)) item = (item & 7) * per + (item >> 3);
+    }
+    const int k = batch_scene_of(BL, item);
+    const BatchScene& D = batch_desc(BL, k);
+    const MpmPtrs S = D.S;
+    const StepParams sp = const_view(D.sp + BL.step);
+    const PModSet& pms = D.pms;
+    item -= BL.first[k];
+#include "mpm_block_body.h"
+}
+
+template <int RB>
+__global__ __launch_bounds__(64) void mpm_grid_block_batch_kernel(BatchLaunch L) {
+    const int slot = (int)blockIdx.x;
+    const int k = batch_scene_of(L, slot);
+    const BatchScene& D = batch_desc(L, k);
+    const BCSet& bcs = const_view(reinterpret_cast<const BCSet*>(D.bcs + (size_t)L.step * (size_t)D.bc_stride));
+    grid_block_update<RB>(D.S, const_view(D.sp + L.step), bcs, slot - L.first[k], D.S.gout);
+}
+
 // export of grid_m / grid_v_in while a P2G is pending (tiles not yet consumed by the grid kernel)
 __global__ __launch_bounds__(64) void grid_export_pending_kernel(MpmPtrs S, float* __restrict__ out, int what) {
     const int Bz = blockIdx.x % S.nbk, By = (blockIdx.x / S.nbk) % S.nbk, Bx = blockIdx.x / (S.nbk * S.nbk);
@@ -1866,29 +1786,32 @@ bool find_field(pixie_mpm* h, const std::string& name, FieldInfo* fi) {
 }
 
 // The BCs of one launch, as the kernels take them
-BCSet make_bcset(const pixie_mpm* h, size_t first) {
+BCSet make_bcset(const std::vector<BCDev>& bcs_dev, size_t first) {
     BCSet set{};
-    set.n = (int)std::min<size_t>(kMaxBCPerLaunch, h->bcs_dev.size() - std::min(first, h->bcs_dev.size()));
-    for (int k = 0; k < set.n; ++k) set.bc[k] = h->bcs_dev[first + k];
+    set.n = (int)std::min<size_t>(kMaxBCPerLaunch, bcs_dev.size() - std::min(first, bcs_dev.size()));
+    for (int k = 0; k < set.n; ++k) set.bc[k] = bcs_dev[first + k];
     return set;
 }
+BCSet make_bcset(const pixie_mpm* h, size_t first) { return make_bcset(h->bcs_dev, first); }
 
 // host `modify` of moving cuboids (mpm_solver_warp.py:899-905) after the grid update of the substep at h->time:
 // python-float maths, stored as f32
-void advance_bcs(pixie_mpm* h, double dt) {
-    for (size_t k = 0; k < h->bcs.size(); ++k) {
-        pixie_bc_desc& b = h->bcs[k];
+// (on explicit state: pixie_mpm_batch_step runs it ahead on copies to precompute a call's BC table)
+void advance_bcs_state(double time, std::vector<pixie_bc_desc>& bcs, std::vector<BCDev>& bcs_dev, double dt) {
+    for (size_t k = 0; k < bcs.size(); ++k) {
+        pixie_bc_desc& b = bcs[k];
         if (b.type != PIXIE_BC_CUBOID) continue;
         const double t0 = (double)(float)b.start_time, t1 = (double)(float)b.end_time;
-        if (h->time >= t0 && h->time < t1) {
+        if (time >= t0 && time < t1) {
             for (int d = 0; d < 3; ++d) {
-                const float np = (float)((double)h->bcs_dev[k].point[d] + dt * (double)h->bcs_dev[k].velocity[d]);
-                h->bcs_dev[k].point[d] = np;
+                const float np = (float)((double)bcs_dev[k].point[d] + dt * (double)bcs_dev[k].velocity[d]);
+                bcs_dev[k].point[d] = np;
                 b.point[d] = np;
             }
         }
     }
 }
+void advance_bcs(pixie_mpm* h, double dt) { advance_bcs_state(h->time, h->bcs, h->bcs_dev, dt); }
 
 template <bool G, bool P, int OCC, int FL>
 void launch_block(const pixie_mpm* h, dim3 grid, hipStream_t st, const StepParams& sp, const PModSet& pms) {
@@ -1901,72 +1824,103 @@ void launch_block_p(const pixie_mpm* h, bool pack, dim3 grid, hipStream_t st, co
     else launch_block<G, P, OCC, BASE>(h, grid, st, sp, pms);
 }
 
+// Which fused G2P + P2G kernel the scene calls for (the variants differ in instruction order, not only in speed: a scene keeps its
+// variant in a batched launch too).  Latency-optimised variant (no scheduling barriers, 130 VGPRs = three waves per SIMD = three
+// 256-thread work items per CU at once): up to that many the whole work list is resident in one round and a launch lasts one work
+// item's latency.
+enum FusedVariant { FV_FIVE_WAVES = 0, FV_WIDE = 1, FV_SIX_WAVES = 2 };
+FusedVariant fused_variant(const pixie_mpm* h) {
+    const bool wide = h->wide == 1 || (h->wide < 0 && h->n_items <= 3 * h->n_cus);
+    if (wide) return FV_WIDE;
+    if (h->occupancy >= 6 && h->scatter_bits != 32) return FV_SIX_WAVES;   // six waves per SIMD: the exact scatter only (the one measured and tested)
+    return FV_FIVE_WAVES;
+}
+
 // the fused G2P + P2G launch in the variant the scene calls for
 void launch_fused_block(const pixie_mpm* h, hipStream_t st, const StepParams& sp, const PModSet& pms) {
     const dim3 grid((unsigned)std::max(h->n_items, 1));
     const bool pack = h->scatter_bits == 32;
-    // Latency-optimised variant (no scheduling barriers, 130 VGPRs = three waves per SIMD = three 256-thread work items per CU at
-    // once): up to that many the whole work list is resident in one round and a launch lasts one work item's latency.
-    const bool wide = h->wide == 1 || (h->wide < 0 && h->n_items <= 3 * h->n_cus);
 #ifdef PIXIE_DIAG
     if (h->trace & ~4) { launch_block_p<true, true, 5, F_TRACE>(h, pack, grid, st, sp, pms); return; }
 #endif
-    if (wide) launch_block_p<true, true, 2, F_WIDE>(h, pack, grid, st, sp, pms);
-    else if (h->occupancy >= 6 && !pack) launch_block<true, true, 6, 0>(h, grid, st, sp, pms);   // six waves per SIMD: the exact scatter only (the one measured and tested)
+    const FusedVariant fv = fused_variant(h);
+    if (fv == FV_WIDE) launch_block_p<true, true, 2, F_WIDE>(h, pack, grid, st, sp, pms);
+    else if (fv == FV_SIX_WAVES) launch_block<true, true, 6, 0>(h, grid, st, sp, pms);
     else launch_block_p<true, true, 5, 0>(h, pack, grid, st, sp, pms);
 }
 
-// particle modifiers whose window contains `time` (float compare, as the kernels do), impulses first (mpm_solver_warp.py:529-547)
-std::vector<PModDev> active_pmods(const pixie_mpm* h, float time) {
+// particle modifiers whose window contains `time` (float compare, as the kernels do), impulses first (mpm_solver_warp.py:529-547);
+// `all`: every registered modifier in that order (the batched kernels, where apply_pmod checks the windows)
+std::vector<PModDev> active_pmods(const pixie_mpm* h, float time, bool all = false) {
     std::vector<PModDev> ordered;
     for (int pass = 0; pass < 2; ++pass)
         for (size_t k = 0; k < h->pmods.size(); ++k) {
             const PModDev& pm = h->pmods[k];
             if ((pm.type == PIXIE_PM_IMPULSE) != (pass == 0)) continue;
-            if (!(time >= pm.start && time < pm.end)) continue;
+            if (!all && !(time >= pm.start && time < pm.end)) continue;
             ordered.push_back(pm);
         }
     return ordered;
 }
 
-int launch_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipStream_t st) {
+// A substep's launches are split in two: the PLAN part (every decision and every change of host state: re-binning, cadence, modifier
+// selection, parameters, BC motion, time) and the ISSUE part (the launches).  pixie_mpm_step runs both per handle; pixie_mpm_batch_step
+// runs the plan of every scene and issues one launch for all of them.
+struct ParticlePlan {
+    bool g2p = false, p2g = false;
+    bool run = false;          // something to launch (no work items: nothing binned)
+    bool fused_mods = true;    // <= kMaxPModFused active modifiers: applied inside the block kernel
+    StepParams sp{};
+    PModSet pms{};
+    std::vector<PModDev> ordered;
+};
+
+int plan_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipStream_t st, ParticlePlan& pl) {
     // (never while staged tiles are waiting for the grid kernel: the work list they are indexed by must not change)
     if (!h->pending_p2g && (h->needs_sort || (h->resort_interval > 0 && h->steps_since_sort >= h->resort_interval)))
         if (rebin(h, st, g2p)) return 1;
     if (g2p) ++h->steps_since_sort;
+    pl.g2p = g2p; pl.p2g = p2g; pl.sp = sp; pl.pms = PModSet{};
+    // modifiers whose time window cannot contain this substep are dropped on the host
+    pl.ordered = active_pmods(h, sp.time);
+    if (h->resort_auto && !pl.ordered.empty() && !h->pmods_were_active)   // a modifier switches on: velocities may jump
+        h->resort_interval = std::min(h->resort_interval, 4);
+    h->pmods_were_active = !pl.ordered.empty();
+    pl.fused_mods = pl.ordered.size() <= (size_t)kMaxPModFused;
+    if (pl.fused_mods) {
+        pl.pms.n = (int)pl.ordered.size();
+        for (int k = 0; k < pl.pms.n; ++k) pl.pms.pm[k] = pl.ordered[k];
+    }
+    pl.run = h->n_items != 0;  // no particles binned (n_particles > 0 always gives >= 1 item)
+    if (pl.run && p2g) h->pending_p2g = true;
+    return 0;
+}
+
+int issue_particle(pixie_mpm* h, const ParticlePlan& pl, hipStream_t st) {
+    if (!pl.run) return 0;
+    const bool g2p = pl.g2p, p2g = pl.p2g;
+    const StepParams& sp = pl.sp;
     const int blocks = cdiv(h->S.n, 256);
     const dim3 grid((unsigned)std::max(h->n_items, 1));
-    PModSet pms{};
-    // modifiers whose time window cannot contain this substep are dropped on the host
-    std::vector<PModDev> ordered = active_pmods(h, sp.time);
-    if (h->resort_auto && !ordered.empty() && !h->pmods_were_active)   // a modifier switches on: velocities may jump
-        h->resort_interval = std::min(h->resort_interval, 4);
-    h->pmods_were_active = !ordered.empty();
-    const bool fused_mods = ordered.size() <= (size_t)kMaxPModFused;
-    if (fused_mods) {
-        pms.n = (int)ordered.size();
-        for (int k = 0; k < pms.n; ++k) pms.pm[k] = ordered[k];
-    }
-    if (h->n_items == 0) return 0;  // no particles binned (n_particles > 0 always gives >= 1 item)
     const bool pack = h->scatter_bits == 32;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->profile && p2g && g2p) {
         PX_CHECK_HIP(hipEventCreate(&e0)); PX_CHECK_HIP(hipEventCreate(&e1));
         PX_CHECK_HIP(hipEventRecord(e0, st));
     }
-    if (g2p && p2g && fused_mods) {
-        launch_fused_block(h, st, sp, pms);
+    if (g2p && p2g && pl.fused_mods) {
+        launch_fused_block(h, st, sp, pl.pms);
     } else {
         if (g2p) {
             PModSet none{};
             launch_block<true, false, 5, 0>(h, grid, st, sp, none);
         }
         if (p2g) {
-            if (!fused_mods) {
-                for (const PModDev& m : ordered)
+            if (!pl.fused_mods) {
+                for (const PModDev& m : pl.ordered)
                     hipLaunchKernelGGL(pmod_kernel, dim3(blocks), dim3(256), 0, st, h->S, sp, m);
             }
-            launch_block_p<false, true, 5, 0>(h, pack, grid, st, sp, pms);
+            launch_block_p<false, true, 5, 0>(h, pack, grid, st, sp, pl.pms);
         }
     }
     if (e0) {
@@ -1974,8 +1928,13 @@ int launch_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipS
         h->ev_particle.emplace_back(e0, e1);
     }
     PX_CHECK_HIP(hipGetLastError());
-    if (p2g) h->pending_p2g = true;
     return 0;
+}
+
+int launch_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipStream_t st) {
+    static thread_local ParticlePlan pl;   // (re-used: no allocation per launch on the solo path)
+    if (plan_particle(h, g2p, p2g, sp, st, pl)) return 1;
+    return issue_particle(h, pl, st);
 }
 
 void launch_grid_blocks(const pixie_mpm* h, hipStream_t st, const StepParams& sp, const BCSet& set, int mode, int n_wg) {
@@ -1986,14 +1945,23 @@ void launch_grid_blocks(const pixie_mpm* h, hipStream_t st, const StepParams& sp
     else hipLaunchKernelGGL(mpm_grid_block_kernel<4>, g, b, 0, st, h->S, sp, set, mode);
 }
 
-int launch_grid(pixie_mpm* h, const StepParams& sp, double dt, hipStream_t st) {
-    const long total = (long)h->S.ng * h->S.ng * h->S.ng;
-    const int blocks = cdiv(total, 256);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->profile) {
-        PX_CHECK_HIP(hipEventCreate(&e0)); PX_CHECK_HIP(hipEventCreate(&e1));
-        PX_CHECK_HIP(hipEventRecord(e0, st));
-    }
+// One launch of a grid update: the active-block kernel (mode 0 = update, 1 = refresh the inactive blocks) or the dense kernel
+struct GridOp {
+    bool blocks;
+    int mode;        // blocks: mode; dense: normalise
+    int n_wg;        // blocks: workgroups
+    BCSet set;
+};
+struct GridPlan {
+    StepParams sp{};
+    std::vector<GridOp> ops;
+    // the common case, and the only one pixie_mpm_batch_step issues batched: one active-block update with every BC
+    bool single_block_update() const { return ops.size() == 1 && ops[0].blocks && ops[0].mode == 0; }
+};
+
+int plan_grid(pixie_mpm* h, const StepParams& sp, double dt, GridPlan& gp) {
+    gp.sp = sp;
+    gp.ops.clear();
     const size_t nbc = h->bcs_dev.size();
     size_t done = 0;
     int normalise = 1;
@@ -2001,29 +1969,50 @@ int launch_grid(pixie_mpm* h, const StepParams& sp, double dt, hipStream_t st) {
         const BCSet set = make_bcset(h, done);
         if (normalise && h->pending_p2g && nbc <= (size_t)kMaxBCPerLaunch) {
             // staged tiles of the last P2G + slow-path atomics in gin; blocks with nothing nearby are skipped
-            launch_grid_blocks(h, st, sp, set, 0, std::max(h->n_active, 1));
+            gp.ops.push_back(GridOp{true, 0, std::max(h->n_active, 1), set});
             h->gout_sparse = true;
             h->last_grid_sp = sp;
             h->last_grid_bcs.assign(h->bcs_dev.begin(), h->bcs_dev.end());
         } else if (normalise && h->pending_p2g) {  // more BCs than one launch carries: dense follow-up passes need every block
-            launch_grid_blocks(h, st, sp, set, 0, std::max(h->n_active, 1));
-            launch_grid_blocks(h, st, sp, set, 1, h->nblocks);
+            gp.ops.push_back(GridOp{true, 0, std::max(h->n_active, 1), set});
+            gp.ops.push_back(GridOp{true, 1, h->nblocks, set});
             h->gout_sparse = false;
         } else {                          // nothing staged (or a further pass of BCs over gout)
-            hipLaunchKernelGGL(mpm_grid_kernel, dim3(blocks), dim3(256), 0, st, h->S, sp, set, normalise);
+            gp.ops.push_back(GridOp{false, normalise, 0, set});
             if (normalise) h->gout_sparse = false;
         }
         done += set.n;
         normalise = 0;
     } while (done < nbc);
     h->pending_p2g = false;
+    advance_bcs(h, dt);
+    return 0;
+}
+
+int issue_grid(pixie_mpm* h, const GridPlan& gp, hipStream_t st) {
+    const long total = (long)h->S.ng * h->S.ng * h->S.ng;
+    const int blocks = cdiv(total, 256);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->profile) {
+        PX_CHECK_HIP(hipEventCreate(&e0)); PX_CHECK_HIP(hipEventCreate(&e1));
+        PX_CHECK_HIP(hipEventRecord(e0, st));
+    }
+    for (const GridOp& op : gp.ops) {
+        if (op.blocks) launch_grid_blocks(h, st, gp.sp, op.set, op.mode, op.n_wg);
+        else hipLaunchKernelGGL(mpm_grid_kernel, dim3(blocks), dim3(256), 0, st, h->S, gp.sp, op.set, op.mode);
+    }
     if (e0) {
         PX_CHECK_HIP(hipEventRecord(e1, st));
         h->ev_grid.emplace_back(e0, e1);
     }
     PX_CHECK_HIP(hipGetLastError());
-    advance_bcs(h, dt);
     return 0;
+}
+
+int launch_grid(pixie_mpm* h, const StepParams& sp, double dt, hipStream_t st) {
+    static thread_local GridPlan gp;       // (re-used: no allocation per launch on the solo path)
+    if (plan_grid(h, sp, dt, gp)) return 1;
+    return issue_grid(h, gp, st);
 }
 
 // Everything whose size depends on n_grid: the two grid arrays, the block tables and the work list / staged tiles.
@@ -2081,6 +2070,229 @@ int alloc_grid(pixie_mpm* h, int n_grid, double grid_lim) {
     h->pending_p2g = false; h->dirty_grid = false; h->gout_sparse = false;
     if (h->resort_auto) h->resort_interval = 4;
     return rc;
+}
+
+}  // namespace
+
+// Several scenes stepped with one block-kernel and one grid-kernel launch per substep (see BatchScene for the device side).
+struct pixie_mpm_batch {
+    std::vector<pixie_mpm*> h;
+    std::vector<MpmPtrs> desc_S;             // each scene's MpmPtrs as last uploaded (byte copies: compared with memcmp)
+    unsigned char* d_tab = nullptr;          // descriptors, then this call's StepParams tables and BCSet records
+    unsigned char* h_tab = nullptr;          // pinned staging image of d_tab for the current call: h_buf[cur_buf]
+    unsigned char* h_buf[2] = {nullptr, nullptr};   // two, used by alternate calls: a call waits only for the copies of the call before last
+    size_t cap = 0;
+    std::vector<size_t> sp_off;              // this call's StepParams table of scene s, in d_tab / h_tab
+    hipEvent_t ev_up[2] = {nullptr, nullptr};      // after the last copy out of h_buf[i] (h_buf[i] is rewritten only once it has run)
+    int cur_buf = 1;
+    int device = 0;                          // the HIP device current at creation: the events and tables live there
+    hipEvent_t finished = nullptr;           // after the last launch of the last call (d_tab is freed / reallocated only then)
+    int n_cus = 256;
+};
+
+namespace {
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// what a batched step does not cover (the fallbacks of launch_grid / launch_particle, the diagnostic kernels); checked before
+// anything is launched or changed
+int batch_check_handle(const pixie_mpm* h, int s, const char* what) {
+    PX_REQUIRE(!h->dirty_grid, "%s: scene %d has a phase-API P2G pending", what, s);
+    PX_REQUIRE(h->trace == 0, "%s: scene %d has `trace` set (the diagnostic kernels are not batched)", what, s);
+    PX_REQUIRE(h->bcs_dev.size() <= (size_t)kMaxBCPerLaunch, "%s: scene %d has %zu boundary conditions; a batched step takes at most %d per scene",
+               what, s, h->bcs_dev.size(), kMaxBCPerLaunch);
+    PX_REQUIRE(h->pmods.size() <= (size_t)kMaxPModFused, "%s: scene %d has %zu particle modifiers; a batched step takes at most %d per scene",
+               what, s, h->pmods.size(), kMaxPModFused);
+    return 0;
+}
+
+// Start of a call: the descriptors and this call's tables -- StepParams of substeps 0..n and the BCSet of grid launches 0..n-1 -- are
+// computed on the host by running the solo step's own time / BC bookkeeping (make_params, make_bcset, advance_bcs_state) ahead on
+// copies, and uploaded in one copy.  The plan of every substep checks what it computes against these tables (batch_expect_*).
+int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    std::vector<size_t> bc_off(ns), bc_stride(ns);
+    b->sp_off.assign(ns, 0);
+    size_t off = align_up(sizeof(BatchScene) * ns, 256);
+    for (int s = 0; s < ns; ++s) {
+        b->sp_off[s] = off;
+        off = align_up(off + (size_t)(n_sub + 1) * sizeof(StepParams), 16);
+    }
+    const size_t head = offsetof(BCSet, bc);
+    for (int s = 0; s < ns; ++s) {
+        const pixie_mpm* h = b->h[s];
+        const size_t rec = align_up(head + h->bcs_dev.size() * sizeof(BCDev), 16);
+        bool moving = false;
+        for (const pixie_bc_desc& bc : h->bcs) moving = moving || bc.type == PIXIE_BC_CUBOID;
+        bc_stride[s] = moving ? rec : 0;
+        bc_off[s] = off;
+        off += moving ? rec * (size_t)n_sub : rec;
+    }
+    b->cur_buf ^= 1;
+    PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf]));   // the copies of the call before last (a no-op for an event never recorded)
+    if (off > b->cap) {
+        // launches of the last call may still read d_tab, and its copies may still read the other staging buffer
+        PX_CHECK_HIP(hipEventSynchronize(b->finished));
+        PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf ^ 1]));
+        if (b->d_tab) (void)hipFree(b->d_tab);
+        for (unsigned char*& hb : b->h_buf) { if (hb) (void)hipHostFree(hb); hb = nullptr; }
+        b->d_tab = nullptr; b->cap = 0;
+        const size_t cap = align_up(off + off / 2, 4096);
+        PX_CHECK_HIP(hipMalloc((void**)&b->d_tab, cap));
+        for (unsigned char*& hb : b->h_buf) PX_CHECK_HIP(hipHostMalloc((void**)&hb, cap));
+        b->cap = cap;
+    }
+    b->h_tab = b->h_buf[b->cur_buf];
+    b->desc_S.resize(ns);
+    for (int s = 0; s < ns; ++s) {
+        pixie_mpm* h = b->h[s];
+        BatchScene D;
+        memset(&D, 0, sizeof D);
+        memcpy(&D.S, &h->S, sizeof(MpmPtrs));
+        memcpy(&b->desc_S[s], &h->S, sizeof(MpmPtrs));
+        const std::vector<PModDev> all = active_pmods(h, 0.0f, true);
+        D.pms.n = (int)all.size();
+        for (int k = 0; k < D.pms.n; ++k) D.pms.pm[k] = all[k];
+        D.sp = reinterpret_cast<const StepParams*>(b->d_tab + b->sp_off[s]);
+        D.bcs = b->d_tab + bc_off[s];
+        D.bc_stride = (long long)bc_stride[s];
+        memcpy(b->h_tab + s * sizeof(BatchScene), &D, sizeof D);
+        double t = h->time;
+        std::vector<pixie_bc_desc> bcs = h->bcs;
+        std::vector<BCDev> bcs_dev = h->bcs_dev;
+        StepParams* spt = reinterpret_cast<StepParams*>(b->h_tab + b->sp_off[s]);
+        spt[0] = make_params(h, dt, t);
+        for (int i = 0; i < n_sub; ++i) {       // the order of pixie_mpm_step: grid launch at t, `modify`, t += dt, G2P/P2G at t
+            if (bc_stride[s] || i == 0) {
+                const BCSet set = make_bcset(bcs_dev, 0);
+                memcpy(b->h_tab + bc_off[s] + (size_t)i * bc_stride[s], &set, head + (size_t)set.n * sizeof(BCDev));
+            }
+            advance_bcs_state(t, bcs, bcs_dev, dt);
+            t = t + dt;
+            spt[i + 1] = make_params(h, dt, t);
+        }
+    }
+    PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, off, hipMemcpyHostToDevice, st));
+    PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
+    return 0;
+}
+
+int batch_expect_sp(const pixie_mpm_batch* b, int s, int step, const StepParams& sp) {
+    const StepParams* spt = reinterpret_cast<const StepParams*>(b->h_tab + b->sp_off[s]);
+    PX_REQUIRE(memcmp(&spt[step], &sp, sizeof sp) == 0, "pixie_mpm_batch_step: scene %d: parameters of substep %d differ from the call's table (internal error)", s, step);
+    return 0;
+}
+int batch_expect_bcs(const pixie_mpm_batch* b, int s, int step, const BCSet& set) {
+    const BatchScene* D = reinterpret_cast<const BatchScene*>(b->h_tab) + s;
+    const unsigned char* rec = b->h_tab + (D->bcs - b->d_tab) + (size_t)step * (size_t)D->bc_stride;
+    PX_REQUIRE(memcmp(rec, &set, offsetof(BCSet, bc) + (size_t)set.n * sizeof(BCDev)) == 0,
+               "pixie_mpm_batch_step: scene %d: BCs of substep %d differ from the call's table (internal error)", s, step);
+    return 0;
+}
+
+// After the plan of a launch: a scene whose MpmPtrs changed (a re-binning: new row copy, sparse-tile mode) gets its descriptor
+// rewritten.  rebin() ends with a stream synchronisation, so nothing in flight reads the descriptors or copies out of h_tab;
+// the synchronisation below is that guarantee made explicit and costs nothing then.
+int batch_refresh(pixie_mpm_batch* b, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    bool changed = false;
+    for (int s = 0; s < ns; ++s) changed = changed || memcmp(&b->desc_S[s], &b->h[s]->S, sizeof(MpmPtrs)) != 0;
+    if (!changed) return 0;
+    PX_CHECK_HIP(hipStreamSynchronize(st));
+    for (int s = 0; s < ns; ++s) {
+        memcpy(&b->desc_S[s], &b->h[s]->S, sizeof(MpmPtrs));
+        memcpy(b->h_tab + s * sizeof(BatchScene) + offsetof(BatchScene, S), &b->h[s]->S, sizeof(MpmPtrs));
+    }
+    PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, (size_t)ns * sizeof(BatchScene), hipMemcpyHostToDevice, st));
+    PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
+    return 0;
+}
+
+template <bool G, bool P, int OCC, int FL>
+void launch_block_batch(const BatchLaunch& L, unsigned n_wg, int cap, hipStream_t st) {
+    hipLaunchKernelGGL((mpm_block_batch_kernel<G, P, OCC, FL>), dim3(n_wg), dim3((unsigned)cap), 0, st, L);
+}
+
+// One block-kernel launch per group of scenes that share a kernel variant: the work-item capacity (blockDim), when the launch
+// scatters the scatter mode, and for the fused launch each scene's own fused_variant (the wide and the five-wave kernels round
+// differently: test_latency_optimised_variant_matches).  The XCD remap does not change bits and is chosen for the launch (on when
+// every scene has it on).
+int batch_issue_particle(pixie_mpm_batch* b, const std::vector<ParticlePlan>& pl, int step, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    std::vector<char> done(ns, 0);
+    for (int s0 = 0; s0 < ns; ++s0) {
+        if (done[s0] || !pl[s0].run) continue;
+        const pixie_mpm* h0 = b->h[s0];
+        const int cap = h0->item_cap;
+        const bool pack = h0->scatter_bits == 32;
+        const bool g2p = pl[s0].g2p, p2g = pl[s0].p2g;
+        const FusedVariant fv = fused_variant(h0);
+        BatchLaunch L;
+        memset(&L, 0, sizeof L);
+        L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
+        L.step = step;
+        L.xcd_order = 1;
+        long total = 0;
+        for (int s = s0; s < ns; ++s) {
+            const pixie_mpm* h = b->h[s];
+            if (done[s] || !pl[s].run || h->item_cap != cap || (p2g && (h->scatter_bits == 32) != pack)) continue;
+            if (g2p && p2g && fused_variant(h) != fv) continue;
+            done[s] = 1;
+            L.scene[L.n] = s;
+            L.first[L.n] = (int)total;
+            total += h->n_items;
+            if (!h->xcd_order) L.xcd_order = 0;
+            ++L.n;
+        }
+        PX_REQUIRE(total < (long)INT_MAX, "pixie_mpm_batch_step: %ld work items in one launch", total);
+        L.first[L.n] = (int)total;
+        const unsigned n_wg = (unsigned)total;
+        if (g2p && p2g) {
+            if (fv == FV_WIDE && pack) launch_block_batch<true, true, 2, F_WIDE | F_PACK32>(L, n_wg, cap, st);
+            else if (fv == FV_WIDE) launch_block_batch<true, true, 2, F_WIDE>(L, n_wg, cap, st);
+            else if (fv == FV_SIX_WAVES) launch_block_batch<true, true, 6, 0>(L, n_wg, cap, st);
+            else if (pack) launch_block_batch<true, true, 5, F_PACK32>(L, n_wg, cap, st);
+            else launch_block_batch<true, true, 5, 0>(L, n_wg, cap, st);
+        } else if (g2p) {
+            launch_block_batch<true, false, 5, 0>(L, n_wg, cap, st);
+        } else if (pack) {
+            launch_block_batch<false, true, 5, F_PACK32>(L, n_wg, cap, st);
+        } else {
+            launch_block_batch<false, true, 5, 0>(L, n_wg, cap, st);
+        }
+        PX_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// One grid-kernel launch for every scene whose plan is the plain active-block update (every scene, given batch_check_handle: a
+// scene with staged tiles and <= kMaxBCPerLaunch BCs); anything else is issued as the solo step would.  RB from the launch's total.
+int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, int step, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    BatchLaunch L;
+    memset(&L, 0, sizeof L);
+    L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
+    L.step = step;
+    long total = 0;
+    for (int s = 0; s < ns; ++s) {
+        if (!gp[s].single_block_update()) {
+            if (issue_grid(b->h[s], gp[s], st)) return 1;
+            continue;
+        }
+        if (batch_expect_bcs(b, s, step, gp[s].ops[0].set)) return 1;
+        L.scene[L.n] = s;
+        L.first[L.n] = (int)total;
+        total += gp[s].ops[0].n_wg;
+        ++L.n;
+    }
+    if (L.n == 0) return 0;
+    PX_REQUIRE(total < (long)INT_MAX, "pixie_mpm_batch_step: %ld active blocks in one launch", total);
+    L.first[L.n] = (int)total;
+    const dim3 g((unsigned)total), blk(64);
+    if (total > 8L * b->n_cus) hipLaunchKernelGGL(mpm_grid_block_batch_kernel<1>, g, blk, 0, st, L);   // grid_kernel_crowded
+    else hipLaunchKernelGGL(mpm_grid_block_batch_kernel<4>, g, blk, 0, st, L);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace
@@ -2415,6 +2627,88 @@ int pixie_mpm_step(pixie_mpm* h, double dt, int n_substeps, void* stream) {
         // G2P of substep i fused with modifiers/stress/P2G of substep i+1 (evaluated at the new time)
         if (launch_particle(h, true, !last, make_params(h, dt, h->time), st)) return 1;
     }
+    return 0;
+}
+
+int pixie_mpm_batch_create(pixie_mpm_batch** out, pixie_mpm* const* handles, int n_handles) {
+    PX_REQUIRE(out, "pixie_mpm_batch_create: null output pointer");
+    *out = nullptr;
+    PX_REQUIRE(handles, "pixie_mpm_batch_create: null handle list");
+    PX_REQUIRE(n_handles >= 1 && n_handles <= kMaxBatch, "pixie_mpm_batch_create: %d scenes; a batch holds 1 ... %d", n_handles, kMaxBatch);
+    for (int i = 0; i < n_handles; ++i) {
+        PX_REQUIRE(handles[i], "pixie_mpm_batch_create: scene %d is a null handle", i);
+        for (int j = 0; j < i; ++j) PX_REQUIRE(handles[j] != handles[i], "pixie_mpm_batch_create: scenes %d and %d are the same handle", j, i);
+    }
+    for (int i = 0; i < n_handles; ++i)
+        if (batch_check_handle(handles[i], i, "pixie_mpm_batch_create")) return 1;
+    pixie_mpm_batch* b = new pixie_mpm_batch();
+    b->h.assign(handles, handles + n_handles);
+    b->n_cus = handles[0]->n_cus;
+    if (hipGetDevice(&b->device) != hipSuccess ||
+        hipEventCreateWithFlags(&b->ev_up[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&b->ev_up[1], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&b->finished, hipEventDisableTiming) != hipSuccess) {
+        pixie_mpm_batch_destroy(b);
+        return set_error("pixie_mpm_batch_create: hipEventCreate failed");
+    }
+    *out = b;
+    return 0;
+}
+
+// Bit for bit what pixie_mpm_step(h, dt, n_substeps, stream) does to each scene alone: the same plan (plan_particle / plan_grid, in
+// the same order per scene), the same kernel bodies, the same per-scene parameters; only the launches are shared.
+int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* stream) {
+    PX_REQUIRE(b && n_substeps >= 0, "pixie_mpm_batch_step: bad arguments");
+    if (n_substeps == 0) return 0;
+    const int ns = (int)b->h.size();
+    for (int s = 0; s < ns; ++s)
+        if (batch_check_handle(b->h[s], s, "pixie_mpm_batch_step")) return 1;
+    int dev = -1;
+    PX_CHECK_HIP(hipGetDevice(&dev));
+    PX_REQUIRE(dev == b->device, "pixie_mpm_batch_step: HIP device %d is current, the batch was created on device %d", dev, b->device);
+    hipStream_t st = as_stream(stream);
+    if (batch_upload(b, dt, n_substeps, st)) return 1;
+    std::vector<ParticlePlan> pp(ns);
+    std::vector<GridPlan> gp(ns);
+    // substep 0: modifiers + stress + P2G at time t0
+    for (int s = 0; s < ns; ++s) {
+        pixie_mpm* h = b->h[s];
+        const StepParams sp = make_params(h, dt, h->time);
+        if (batch_expect_sp(b, s, 0, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
+    }
+    if (batch_refresh(b, st) || batch_issue_particle(b, pp, 0, st)) return 1;
+    for (int i = 0; i < n_substeps; ++i) {
+        for (int s = 0; s < ns; ++s) {
+            pixie_mpm* h = b->h[s];
+            const StepParams sp = make_params(h, dt, h->time);
+            if (batch_expect_sp(b, s, i, sp) || plan_grid(h, sp, dt, gp[s])) return 1;
+        }
+        if (batch_issue_grid(b, gp, i, st)) return 1;
+        const bool last = (i == n_substeps - 1);
+        for (int s = 0; s < ns; ++s) {
+            pixie_mpm* h = b->h[s];
+            h->time = h->time + dt;  // mpm_solver_warp.py:637
+            const StepParams sp = make_params(h, dt, h->time);
+            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, true, !last, sp, st, pp[s])) return 1;
+        }
+        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
+    }
+    PX_CHECK_HIP(hipEventRecord(b->finished, st));
+    return 0;
+}
+
+int pixie_mpm_batch_destroy(pixie_mpm_batch* b) {
+    if (!b) return 0;
+    if (b->finished) (void)hipEventSynchronize(b->finished);
+    for (hipEvent_t e : b->ev_up)
+        if (e) (void)hipEventSynchronize(e);
+    if (b->d_tab) (void)hipFree(b->d_tab);
+    for (unsigned char* hb : b->h_buf)
+        if (hb) (void)hipHostFree(hb);
+    for (hipEvent_t e : b->ev_up)
+        if (e) (void)hipEventDestroy(e);
+    if (b->finished) (void)hipEventDestroy(b->finished);
+    delete b;
     return 0;
 }
 

@@ -130,12 +130,39 @@ int pixie_mpm_step(pixie_mpm* h, double dt, int n_substeps, void* stream);
  *     pixie_mpm_step(h, dt, n_substeps, stream) gives it alone.  Each handle's state is re-read at the start of every call, so
  *     regrid / set_field / set_scalar / add_bc between calls are picked up.  n_substeps == 0 is a no-op.  Successive calls on
  *     different streams must be ordered by the caller, as for pixie_mpm_step.
- * Both refuse -- with a pixie_last_error message, before anything is launched or changed -- a null or repeated handle, an empty
- * or too long list, a scene with a phase-API P2G pending, with `trace` set, with more than 16 boundary conditions or with more
- * than 8 particle modifiers (the cases pixie_mpm_step serves with extra launches). */
+ *   pixie_mpm_batch_run: per-scene time steps, substep counts and frame exports.  per_scene[s] (n_scenes == the batch's scene
+ *     count) is scene s's frame loop, and scene s ends -- in its state and in every exported frame -- in exactly the bits of
+ *       for (f = 0; f < n_chunks; ++f) {
+ *           if (n_out > 0) pixie_mpm_export_frame(h, n_out, shift, scale, mean, inv_rotation,
+ *                                                 d_pos + f * n_out * 3, d_cov ? d_cov + f * n_out * 6 : NULL, stream);
+ *           pixie_mpm_step(h, dt, steps_per_chunk, stream);
+ *       }
+ *     (a ragged run is n_chunks = 1, n_out = 0; steps_per_chunk * n_chunks == 0 leaves the scene untouched).  Substep j of every
+ *     scene is global step j of the call: one grid-kernel launch per global step covers every scene that still has substeps, so
+ *     a call issues max_s(steps_per_chunk * n_chunks) grid launches; the exports of the scenes that start a frame at the same
+ *     global step are one launch.  Chunk boundaries are kept as given (each is a pixie_mpm_step call of the solo loop).  The
+ *     tables are built and uploaded in windows of 1024 global steps, so a call may be arbitrarily long.  Asynchronous on `stream`
+ *     apart from the synchronisations a re-binning does.  Also refused: dt <= 0 or not finite, negative counts, n_scenes not the
+ *     batch's scene count, n_out < 0 or > the scene's particle count, n_out > 0 with a null d_pos or a zero scale.
+ *     pixie_mpm_batch_step(b, dt, n, stream) is the same call with every scene at (dt, n, 1 chunk, no export).
+ * All three refuse -- with a pixie_last_error message, before anything is launched or changed -- a null or repeated handle, an
+ * empty or too long list, a scene with a phase-API P2G pending, with `trace` set, with more than 16 boundary conditions or with
+ * more than 8 particle modifiers (the cases pixie_mpm_step serves with extra launches). */
 typedef struct pixie_mpm_batch pixie_mpm_batch;
+typedef struct pixie_batch_sched {
+    double dt;                         /* > 0 */
+    int32_t steps_per_chunk;           /* substeps per frame (>= 0) */
+    int32_t n_chunks;                  /* frames (>= 0) */
+    int32_t n_out;                     /* particles exported per frame (caller order); 0: no export */
+    int32_t pad_;
+    double shift[3], scale, mean[3];   /* the export transform of pixie_mpm_export_frame */
+    double inv_rotation[9];
+    float* d_pos;                      /* [n_chunks][n_out][3] */
+    float* d_cov;                      /* [n_chunks][n_out][6] or NULL */
+} pixie_batch_sched;
 int pixie_mpm_batch_create(pixie_mpm_batch** out, pixie_mpm* const* handles, int n_handles);
 int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* stream);
+int pixie_mpm_batch_run(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, int n_scenes, void* stream);
 int pixie_mpm_batch_destroy(pixie_mpm_batch* b);
 
 /* compute_cov_from_F (mpm_utils.py:529-553) and compute_R_from_F (:556-580) as used by

@@ -66,6 +66,13 @@ class UNetConfigC(C.Structure):
                 ("grid_size", C.c_int32), ("out_channels", C.c_int32), ("precision", C.c_int32)]
 
 
+class BatchSched(C.Structure):
+    """struct pixie_batch_sched"""
+    _fields_ = [("dt", C.c_double), ("steps_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("n_out", C.c_int32), ("pad_", C.c_int32),
+                ("shift", C.c_double * 3), ("scale", C.c_double), ("mean", C.c_double * 3), ("inv_rotation", C.c_double * 9),
+                ("d_pos", C.c_void_p), ("d_cov", C.c_void_p)]
+
+
 class FieldDesc(C.Structure):
     """struct pixie_field_desc"""
     _fields_ = [("d_pred", C.c_void_p), ("d_mask", C.c_void_p),
@@ -103,6 +110,7 @@ SIGNATURES = {
     "pixie_mpm_out_of_bounds": (_I, [_VP, C.POINTER(_I64), _VP]),
     "pixie_mpm_batch_create": (_I, [C.POINTER(_VP), C.POINTER(_VP), _I]),
     "pixie_mpm_batch_step": (_I, [_VP, _D, _I, _VP]),
+    "pixie_mpm_batch_run": (_I, [_VP, C.POINTER(BatchSched), _I, _VP]),
     "pixie_mpm_batch_destroy": (_I, [_VP]),
     "pixie_pack_fields": (_I, [_VP, _VP, _I64, _I64, _VP, _I64, _VP]),
     "pixie_conv_cout_padded": (_I, [_I]),

@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <map>
@@ -1225,7 +1226,9 @@ struct BatchLaunch {
 typedef const BatchScene __attribute__((address_space(4))) ConstBatchScene;
 
 // launch scene of global index `g` (wave-uniform: g is a workgroup index), and the descriptor it reads
-__device__ __forceinline__ int batch_scene_of(const BatchLaunch& L, int g) {
+// (Launch: BatchLaunch, or ExportLaunch of the batched frame export)
+template <class Launch>
+__device__ __forceinline__ int batch_scene_of(const Launch& L, int g) {
     int k = 0;
     for (int j = 1; j < L.n; ++j) k += (g >= L.first[j]) ? 1 : 0;
     return __builtin_amdgcn_readfirstlane(k);
@@ -1235,7 +1238,8 @@ template <class T>
 __device__ __forceinline__ const T& const_view(const T* p) {
     return *(const T*)(const T __attribute__((address_space(4)))*)p;
 }
-__device__ __forceinline__ const BatchScene& batch_desc(const BatchLaunch& L, int k) {
+template <class Launch>
+__device__ __forceinline__ const BatchScene& batch_desc(const Launch& L, int k) {
     const ConstBatchScene* d = (const ConstBatchScene*)L.scenes + L.scene[k];
     return *(const BatchScene*)d;
 }
@@ -1455,32 +1459,45 @@ __global__ void cov_kernel(MpmPtrs S, const float* __restrict__ init_cov, float*
 //   pos_render = apply_inverse_rotations(undotransform2origin(undoshift2center111(x, z_shift), scale, mean), Rs)
 //   cov_render = apply_inverse_cov_rotations(compute_cov_from_F(F_trial, init_cov) / scale^2, Rs)
 // (PG/utils/transformation_utils.py:19-20,108-130; compute_cov_from_F mpm_utils.py:529-553) with the rotation chain
-// folded into one matrix M on the host: pos @ M, M^T cov M.
+// folded into one matrix M on the host: pos @ M, M^T cov M.  The body is shared textually with frame_export_batch_kernel.
 struct FrameXform { float shift[3]; float inv_scale; float mean[3]; float inv_scale2; float M[9]; };
 __global__ void frame_export_kernel(MpmPtrs S, const float* __restrict__ init_cov, FrameXform X, int n_out, float* __restrict__ pos_out,
                                     float* __restrict__ cov_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const int s = S.perm[i];
-    if (s >= n_out) return;
-    float q[3];
-    for (int d = 0; d < 3; ++d) q[d] = X.mean[d] + (S.x[(size_t)d * S.n + i] - X.shift[d]) * X.inv_scale;
-    for (int d = 0; d < 3; ++d) pos_out[(size_t)s * 3 + d] = q[0] * X.M[d] + q[1] * X.M[3 + d] + q[2] * X.M[6 + d];
-    if (!cov_out) return;
-    Mat3 F, C0, M;
-    for (int c = 0; c < 9; ++c) { F.m[c] = S.Ft[(size_t)c * S.n + i]; M.m[c] = X.M[c]; }
-    const float* c6 = init_cov + (size_t)s * 6;
-    C0.m[0] = c6[0]; C0.m[1] = c6[1]; C0.m[2] = c6[2];
-    C0.m[3] = c6[1]; C0.m[4] = c6[3]; C0.m[5] = c6[4];
-    C0.m[6] = c6[2]; C0.m[7] = c6[4]; C0.m[8] = c6[5];
-    Mat3 T = mat_mul_bt(mat_mul(F, C0), F);                 // F C0 F^T
-    for (int c = 0; c < 9; ++c) T.m[c] *= X.inv_scale2;
-    // M^T T M
-    Mat3 Mt;
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) Mt.m[3 * a + b] = M.m[3 * b + a];
-    const Mat3 Rr = mat_mul(mat_mul(Mt, T), M);
-    float* o = cov_out + (size_t)s * 6;
-    o[0] = Rr.m[0]; o[1] = Rr.m[1]; o[2] = Rr.m[2]; o[3] = Rr.m[4]; o[4] = Rr.m[5]; o[5] = Rr.m[8];
+#include "frame_export_body.h"
+}
+// The same export for several scenes of a pixie_mpm_batch in one launch (pixie_mpm_batch_run): one record per scene in the call's
+// table (BatchExport), and a launch argument that says which scenes export which frame.  Block b of the launch belongs to launch
+// scene k with first[k] <= b < first[k + 1] (ceil(n / 256) blocks per scene, as frame_export_kernel's grid).
+struct BatchExport {
+    FrameXform X;
+    const float* init_cov;
+    float* pos;                    // frame 0 of [n_frames][n_out][3]
+    float* cov;                    // frame 0 of [n_frames][n_out][6], or NULL
+    int n_out;
+    int pad;
+};
+struct ExportLaunch {
+    const BatchScene* scenes;      // device descriptors (MpmPtrs kept current by batch_refresh)
+    const BatchExport* ex;         // export record of descriptor s: ex[s]
+    int n;                         // scenes in this launch
+    int pad;
+    int scene[kMaxBatch];          // descriptor of launch scene k
+    int frame[kMaxBatch];          // the frame launch scene k exports
+    int first[kMaxBatch + 1];      // first block of launch scene k
+};
+__global__ void frame_export_batch_kernel(ExportLaunch L) {
+    const int k = batch_scene_of(L, (int)blockIdx.x);
+    // (copied into locals first, as mpm_block_batch_kernel does: the body must see what frame_export_kernel's arguments give it)
+    const MpmPtrs S = batch_desc(L, k).S;
+    const BatchExport E = const_view(L.ex + L.scene[k]);
+    const FrameXform X = E.X;
+    const float* __restrict__ init_cov = E.init_cov;
+    const int n_out = E.n_out;
+    float* __restrict__ pos_out = E.pos + (size_t)L.frame[k] * (size_t)n_out * 3;
+    float* __restrict__ cov_out = E.cov ? E.cov + (size_t)L.frame[k] * (size_t)n_out * 6 : nullptr;
+    const int i = ((int)blockIdx.x - L.first[k]) * 256 + (int)threadIdx.x;
+#include "frame_export_body.h"
 }
 // compute_R_from_F, mpm_utils.py:556-580 (stores R^T)
 __global__ void rot_kernel(MpmPtrs S, float* __restrict__ Rout, const int* perm) {
@@ -2082,7 +2099,8 @@ struct pixie_mpm_batch {
     unsigned char* h_tab = nullptr;          // pinned staging image of d_tab for the current call: h_buf[cur_buf]
     unsigned char* h_buf[2] = {nullptr, nullptr};   // two, used by alternate calls: a call waits only for the copies of the call before last
     size_t cap = 0;
-    std::vector<size_t> sp_off;              // this call's StepParams table of scene s, in d_tab / h_tab
+    std::vector<size_t> sp_off;              // this window's StepParams table of scene s, in d_tab / h_tab
+    size_t ex_off = 0;                       // this call's export records (BatchExport per scene), if it exports
     hipEvent_t ev_up[2] = {nullptr, nullptr};      // after the last copy out of h_buf[i] (h_buf[i] is rewritten only once it has run)
     int cur_buf = 1;
     int device = 0;                          // the HIP device current at creation: the events and tables live there
@@ -2106,17 +2124,36 @@ int batch_check_handle(const pixie_mpm* h, int s, const char* what) {
     return 0;
 }
 
-// Start of a call: the descriptors and this call's tables -- StepParams of substeps 0..n and the BCSet of grid launches 0..n-1 -- are
-// computed on the host by running the solo step's own time / BC bookkeeping (make_params, make_bcset, advance_bcs_state) ahead on
-// copies, and uploaded in one copy.  The plan of every substep checks what it computes against these tables (batch_expect_*).
-int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
+// One call's schedule for one scene (pixie_mpm_batch_run, validated): n_chunks chunks of `chunk` substeps of dt, the scene's
+// substep j being the call's global step j; `exp`: a frame export before every chunk (BatchExport record).
+struct BatchSched {
+    double dt = 0.0;
+    int chunk = 0;
+    int n_chunks = 0;
+    int total = 0;                 // chunk * n_chunks
+    bool exp = false;
+};
+
+// Long calls are tabled in windows of kBatchWindow global steps: a moving cuboid stores one BCSet record (up to ~1.4 KB) per substep,
+// and a 200-frame metal scene is 200 000 substeps.
+constexpr int kBatchWindow = 1024;
+
+// Start of a window [g0, g0 + kBatchWindow) of a call: the descriptors and the window's tables -- per scene, the StepParams of global
+// steps g0 ... g0 + n and the BCSet of grid launches g0 ... g0 + n - 1, n = the scene's substeps in the window -- are computed on the
+// host by running the solo step's own time / BC bookkeeping (make_params, make_bcset, advance_bcs_state) ahead on copies of the
+// handle's state, which the plans of the steps before g0 have brought to global step g0, and uploaded in one copy.  Launches index
+// the tables with the step relative to g0.  The plan of every substep checks what it computes against these tables (batch_expect_*).
+// `ex`: the call's export records, uploaded with every window (NULL: the call does not export).
+int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, const std::vector<BatchExport>* ex, hipStream_t st) {
     const int ns = (int)b->h.size();
     std::vector<size_t> bc_off(ns), bc_stride(ns);
+    std::vector<int> n_win(ns);
     b->sp_off.assign(ns, 0);
     size_t off = align_up(sizeof(BatchScene) * ns, 256);
     for (int s = 0; s < ns; ++s) {
+        n_win[s] = std::max(0, std::min(sc[s].total - g0, kBatchWindow));
         b->sp_off[s] = off;
-        off = align_up(off + (size_t)(n_sub + 1) * sizeof(StepParams), 16);
+        off = align_up(off + (size_t)(n_win[s] + 1) * sizeof(StepParams), 16);
     }
     const size_t head = offsetof(BCSet, bc);
     for (int s = 0; s < ns; ++s) {
@@ -2126,13 +2163,24 @@ int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
         for (const pixie_bc_desc& bc : h->bcs) moving = moving || bc.type == PIXIE_BC_CUBOID;
         bc_stride[s] = moving ? rec : 0;
         bc_off[s] = off;
-        off += moving ? rec * (size_t)n_sub : rec;
+        off += moving ? rec * (size_t)n_win[s] : rec;
     }
+    size_t ex_off = 0;
+    if (ex) {
+        ex_off = off = align_up(off, 16);
+        off += (size_t)ns * sizeof(BatchExport);
+    }
+    // Rewriting d_tab between the windows of a call is safe without a synchronisation: the copy below is issued on `st`, the stream
+    // of every launch of the call, after the last launch of the previous window, and a launch of this window is issued after it.
+    // (The staging buffer is another matter: h_buf[cur_buf] is rewritten only once ev_up says its last copy has run.)
     b->cur_buf ^= 1;
-    PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf]));   // the copies of the call before last (a no-op for an event never recorded)
+    PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf]));   // the copies of the window before last (a no-op for an event never recorded)
     if (off > b->cap) {
-        // launches of the last call may still read d_tab, and its copies may still read the other staging buffer
+        // launches of the last call may still read d_tab, and its copies may still read the other staging buffer.  (Within a call
+        // the first window is the largest -- scenes only drop out -- so this runs at g0 == 0; the stream synchronisation covers the
+        // call's own earlier launches otherwise.)
         PX_CHECK_HIP(hipEventSynchronize(b->finished));
+        if (g0 > 0) PX_CHECK_HIP(hipStreamSynchronize(st));
         PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf ^ 1]));
         if (b->d_tab) (void)hipFree(b->d_tab);
         for (unsigned char*& hb : b->h_buf) { if (hb) (void)hipHostFree(hb); hb = nullptr; }
@@ -2157,12 +2205,13 @@ int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
         D.bcs = b->d_tab + bc_off[s];
         D.bc_stride = (long long)bc_stride[s];
         memcpy(b->h_tab + s * sizeof(BatchScene), &D, sizeof D);
+        const double dt = sc[s].dt;
         double t = h->time;
         std::vector<pixie_bc_desc> bcs = h->bcs;
         std::vector<BCDev> bcs_dev = h->bcs_dev;
         StepParams* spt = reinterpret_cast<StepParams*>(b->h_tab + b->sp_off[s]);
         spt[0] = make_params(h, dt, t);
-        for (int i = 0; i < n_sub; ++i) {       // the order of pixie_mpm_step: grid launch at t, `modify`, t += dt, G2P/P2G at t
+        for (int i = 0; i < n_win[s]; ++i) {    // the order of pixie_mpm_step: grid launch at t, `modify`, t += dt, G2P/P2G at t
             if (bc_stride[s] || i == 0) {
                 const BCSet set = make_bcset(bcs_dev, 0);
                 memcpy(b->h_tab + bc_off[s] + (size_t)i * bc_stride[s], &set, head + (size_t)set.n * sizeof(BCDev));
@@ -2172,6 +2221,8 @@ int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
             spt[i + 1] = make_params(h, dt, t);
         }
     }
+    b->ex_off = ex_off;
+    if (ex) memcpy(b->h_tab + ex_off, ex->data(), (size_t)ns * sizeof(BatchExport));
     PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, off, hipMemcpyHostToDevice, st));
     PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
     return 0;
@@ -2179,14 +2230,14 @@ int batch_upload(pixie_mpm_batch* b, double dt, int n_sub, hipStream_t st) {
 
 int batch_expect_sp(const pixie_mpm_batch* b, int s, int step, const StepParams& sp) {
     const StepParams* spt = reinterpret_cast<const StepParams*>(b->h_tab + b->sp_off[s]);
-    PX_REQUIRE(memcmp(&spt[step], &sp, sizeof sp) == 0, "pixie_mpm_batch_step: scene %d: parameters of substep %d differ from the call's table (internal error)", s, step);
+    PX_REQUIRE(memcmp(&spt[step], &sp, sizeof sp) == 0, "pixie_mpm_batch: scene %d: parameters of window step %d differ from the call's table (internal error)", s, step);
     return 0;
 }
 int batch_expect_bcs(const pixie_mpm_batch* b, int s, int step, const BCSet& set) {
     const BatchScene* D = reinterpret_cast<const BatchScene*>(b->h_tab) + s;
     const unsigned char* rec = b->h_tab + (D->bcs - b->d_tab) + (size_t)step * (size_t)D->bc_stride;
     PX_REQUIRE(memcmp(rec, &set, offsetof(BCSet, bc) + (size_t)set.n * sizeof(BCDev)) == 0,
-               "pixie_mpm_batch_step: scene %d: BCs of substep %d differ from the call's table (internal error)", s, step);
+               "pixie_mpm_batch: scene %d: BCs of window step %d differ from the call's table (internal error)", s, step);
     return 0;
 }
 
@@ -2213,10 +2264,11 @@ void launch_block_batch(const BatchLaunch& L, unsigned n_wg, int cap, hipStream_
     hipLaunchKernelGGL((mpm_block_batch_kernel<G, P, OCC, FL>), dim3(n_wg), dim3((unsigned)cap), 0, st, L);
 }
 
-// One block-kernel launch per group of scenes that share a kernel variant: the work-item capacity (blockDim), when the launch
-// scatters the scatter mode, and for the fused launch each scene's own fused_variant (the wide and the five-wave kernels round
-// differently: test_latency_optimised_variant_matches).  The XCD remap does not change bits and is chosen for the launch (on when
-// every scene has it on).
+// One block-kernel launch per group of scenes that share a kernel variant: the launch kind (g2p, p2g) -- scenes at different points
+// of their schedules are fused, G2P-only (a chunk's last substep) or P2G-only (a chunk's first) at the same global step -- the
+// work-item capacity (blockDim), when the launch scatters the scatter mode, and for the fused launch each scene's own fused_variant
+// (the wide and the five-wave kernels round differently: test_latency_optimised_variant_matches).  The XCD remap does not change bits
+// and is chosen for the launch (on when every scene has it on).  Scenes whose plan has `run` unset take no part.
 int batch_issue_particle(pixie_mpm_batch* b, const std::vector<ParticlePlan>& pl, int step, hipStream_t st) {
     const int ns = (int)b->h.size();
     std::vector<char> done(ns, 0);
@@ -2235,7 +2287,8 @@ int batch_issue_particle(pixie_mpm_batch* b, const std::vector<ParticlePlan>& pl
         long total = 0;
         for (int s = s0; s < ns; ++s) {
             const pixie_mpm* h = b->h[s];
-            if (done[s] || !pl[s].run || h->item_cap != cap || (p2g && (h->scatter_bits == 32) != pack)) continue;
+            if (done[s] || !pl[s].run || pl[s].g2p != g2p || pl[s].p2g != p2g) continue;
+            if (h->item_cap != cap || (p2g && (h->scatter_bits == 32) != pack)) continue;
             if (g2p && p2g && fused_variant(h) != fv) continue;
             done[s] = 1;
             L.scene[L.n] = s;
@@ -2267,7 +2320,8 @@ int batch_issue_particle(pixie_mpm_batch* b, const std::vector<ParticlePlan>& pl
 
 // One grid-kernel launch for every scene whose plan is the plain active-block update (every scene, given batch_check_handle: a
 // scene with staged tiles and <= kMaxBCPerLaunch BCs); anything else is issued as the solo step would.  RB from the launch's total.
-int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, int step, hipStream_t st) {
+// Scenes with `on[s]` unset have no substep at this global step and take no part.
+int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, const std::vector<char>& on, int step, hipStream_t st) {
     const int ns = (int)b->h.size();
     BatchLaunch L;
     memset(&L, 0, sizeof L);
@@ -2275,6 +2329,7 @@ int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, int st
     L.step = step;
     long total = 0;
     for (int s = 0; s < ns; ++s) {
+        if (!on[s]) continue;
         if (!gp[s].single_block_update()) {
             if (issue_grid(b->h[s], gp[s], st)) return 1;
             continue;
@@ -2293,6 +2348,127 @@ int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, int st
     else hipLaunchKernelGGL(mpm_grid_block_batch_kernel<4>, g, blk, 0, st, L);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// One frame_export_batch_kernel launch for every scene with frame[s] >= 0 (the frame it exports); none if there is none.
+int batch_issue_export(pixie_mpm_batch* b, const std::vector<int>& frame, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    ExportLaunch L;
+    memset(&L, 0, sizeof L);
+    L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
+    L.ex = reinterpret_cast<const BatchExport*>(b->d_tab + b->ex_off);
+    long total = 0;
+    for (int s = 0; s < ns; ++s) {
+        if (frame[s] < 0) continue;
+        L.scene[L.n] = s;
+        L.frame[L.n] = frame[s];
+        L.first[L.n] = (int)total;
+        total += cdiv(b->h[s]->S.n, 256);
+        ++L.n;
+    }
+    if (L.n == 0) return 0;
+    L.first[L.n] = (int)total;
+    hipLaunchKernelGGL(frame_export_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The launches of one call.  Every scene runs its chunks with the launch sequence of pixie_mpm_step -- a P2G-only launch, then per
+// substep [grid launch at t, t += dt, fused G2P + P2G, or G2P-only on the chunk's last substep] -- and its substep j is the call's
+// global step j, so the scenes that still have substeps share each global step's grid launch and particle launches (one per
+// variant group).  A scene that ends a chunk at a global step and has another one exports its next frame after that step's particle
+// launches -- its G2P-only launch has left v / C / F_trial valid (the note on skip_vcft); no export is ever issued inside a chunk,
+// frame_export reads F_trial -- and then plans and issues its next chunk's P2G-only launch, so that it joins the next grid launch.
+// Frame 0's export precedes everything.  Chunk boundaries are kept as given: each scene sees exactly the pixie_mpm_step calls
+// (and exports) of its solo loop, in the same order, on its own host state.
+int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const std::vector<BatchExport>& ex, hipStream_t st) {
+    const int ns = (int)b->h.size();
+    int G = 0;
+    bool any_ex = false;
+    for (const BatchSched& q : sc) { G = std::max(G, q.total); any_ex = any_ex || q.exp; }
+    if (G == 0 && !any_ex) return 0;
+    const std::vector<BatchExport>* exr = any_ex ? &ex : nullptr;
+    int g0 = 0;
+    if (batch_upload(b, sc, g0, exr, st)) return 1;
+    std::vector<ParticlePlan> pp(ns);
+    std::vector<GridPlan> gp(ns);
+    std::vector<char> on(ns, 0), next(ns, 0);
+    std::vector<int> frame(ns, -1);
+    // frame 0 of every exporting scene (a scene whose chunks are empty exports all its frames here, one launch per frame)
+    for (int f = 0; any_ex; ++f) {
+        bool any = false;
+        for (int s = 0; s < ns; ++s) {
+            const bool e = sc[s].exp && f < sc[s].n_chunks && (f == 0 || sc[s].chunk == 0);
+            frame[s] = e ? f : -1;
+            any = any || e;
+        }
+        if (!any) break;
+        if (batch_issue_export(b, frame, st)) return 1;
+    }
+    // substep 0 of the first chunk: modifiers + stress + P2G at time t0
+    for (int s = 0; s < ns; ++s) {
+        pp[s].run = false;
+        if (sc[s].total == 0) continue;
+        pixie_mpm* h = b->h[s];
+        const StepParams sp = make_params(h, sc[s].dt, h->time);
+        if (batch_expect_sp(b, s, 0, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
+    }
+    if (batch_refresh(b, st) || batch_issue_particle(b, pp, 0, st)) return 1;
+    for (int g = 0; g < G; ++g) {
+        if (g - g0 == kBatchWindow) {
+            g0 = g;
+            if (batch_upload(b, sc, g0, exr, st)) return 1;
+        }
+        const int i = g - g0;
+        for (int s = 0; s < ns; ++s) {
+            on[s] = g < sc[s].total;
+            if (!on[s]) continue;
+            pixie_mpm* h = b->h[s];
+            const StepParams sp = make_params(h, sc[s].dt, h->time);
+            if (batch_expect_sp(b, s, i, sp) || plan_grid(h, sp, sc[s].dt, gp[s])) return 1;
+        }
+        if (batch_issue_grid(b, gp, on, i, st)) return 1;
+        bool any_next = false;
+        for (int s = 0; s < ns; ++s) {
+            pp[s].run = false;
+            next[s] = 0;
+            frame[s] = -1;
+            if (!on[s]) continue;
+            pixie_mpm* h = b->h[s];
+            h->time = h->time + sc[s].dt;  // mpm_solver_warp.py:637
+            const bool last = (g + 1) % sc[s].chunk == 0;
+            const StepParams sp = make_params(h, sc[s].dt, h->time);
+            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, true, !last, sp, st, pp[s])) return 1;
+            if (last && g + 1 < sc[s].total) {
+                next[s] = 1;
+                any_next = true;
+                if (sc[s].exp) frame[s] = (g + 1) / sc[s].chunk;
+            }
+        }
+        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
+        if (!any_next) continue;
+        // scenes between two chunks: the next frame's export, then the next chunk's P2G-only launch at the same time
+        if (batch_issue_export(b, frame, st)) return 1;
+        for (int s = 0; s < ns; ++s) {
+            pp[s].run = false;
+            if (!next[s]) continue;
+            pixie_mpm* h = b->h[s];
+            const StepParams sp = make_params(h, sc[s].dt, h->time);
+            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
+        }
+        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
+    }
+    PX_CHECK_HIP(hipEventRecord(b->finished, st));
+    return 0;
+}
+
+// the export transform of pixie_mpm_export_frame / pixie_mpm_batch_run (float conversions of the caller's doubles)
+FrameXform make_frame_xform(const double shift[3], double scale, const double mean[3], const double inv_rotation[9]) {
+    FrameXform X{};
+    for (int d = 0; d < 3; ++d) { X.shift[d] = (float)shift[d]; X.mean[d] = (float)mean[d]; }
+    X.inv_scale = (float)(1.0 / scale); X.inv_scale2 = (float)(1.0 / (scale * scale));
+    for (int c = 0; c < 9; ++c) X.M[c] = (float)inv_rotation[c];
+    return X;
 }
 
 }  // namespace
@@ -2666,35 +2842,54 @@ int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* st
     int dev = -1;
     PX_CHECK_HIP(hipGetDevice(&dev));
     PX_REQUIRE(dev == b->device, "pixie_mpm_batch_step: HIP device %d is current, the batch was created on device %d", dev, b->device);
-    hipStream_t st = as_stream(stream);
-    if (batch_upload(b, dt, n_substeps, st)) return 1;
-    std::vector<ParticlePlan> pp(ns);
-    std::vector<GridPlan> gp(ns);
-    // substep 0: modifiers + stress + P2G at time t0
+    // one chunk of n_substeps for every scene: the launches of the scheduler's common case
+    BatchSched q;
+    q.dt = dt; q.chunk = n_substeps; q.n_chunks = 1; q.total = n_substeps;
+    return batch_schedule(b, std::vector<BatchSched>(ns, q), std::vector<BatchExport>(), as_stream(stream));
+}
+
+// Per-scene dt, substep counts and frame exports: each scene s runs, bit for bit, its solo frame loop
+//   for f < n_chunks: [pixie_mpm_export_frame(frame f) if n_out > 0]; pixie_mpm_step(dt, steps_per_chunk)
+// with the launches shared across scenes (batch_schedule).
+int pixie_mpm_batch_run(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, int n_scenes, void* stream) {
+    PX_REQUIRE(b && per_scene, "pixie_mpm_batch_run: null argument");
+    const int ns = (int)b->h.size();
+    PX_REQUIRE(n_scenes == ns, "pixie_mpm_batch_run: %d schedules for a batch of %d scenes", n_scenes, ns);
+    std::vector<BatchSched> sc(ns);
+    std::vector<BatchExport> ex(ns);
+    memset(ex.data(), 0, ex.size() * sizeof(BatchExport));
     for (int s = 0; s < ns; ++s) {
-        pixie_mpm* h = b->h[s];
-        const StepParams sp = make_params(h, dt, h->time);
-        if (batch_expect_sp(b, s, 0, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
-    }
-    if (batch_refresh(b, st) || batch_issue_particle(b, pp, 0, st)) return 1;
-    for (int i = 0; i < n_substeps; ++i) {
-        for (int s = 0; s < ns; ++s) {
-            pixie_mpm* h = b->h[s];
-            const StepParams sp = make_params(h, dt, h->time);
-            if (batch_expect_sp(b, s, i, sp) || plan_grid(h, sp, dt, gp[s])) return 1;
+        const pixie_batch_sched& q = per_scene[s];
+        const pixie_mpm* h = b->h[s];
+        PX_REQUIRE(std::isfinite(q.dt) && q.dt > 0.0, "pixie_mpm_batch_run: scene %d: dt %g (a positive finite time step is required)", s, q.dt);
+        PX_REQUIRE(q.steps_per_chunk >= 0 && q.n_chunks >= 0, "pixie_mpm_batch_run: scene %d: negative counts (%d substeps per chunk, %d chunks)",
+                   s, q.steps_per_chunk, q.n_chunks);
+        PX_REQUIRE((long long)q.steps_per_chunk * q.n_chunks <= (long long)INT_MAX, "pixie_mpm_batch_run: scene %d: %d x %d substeps exceed a call",
+                   s, q.n_chunks, q.steps_per_chunk);
+        PX_REQUIRE(q.n_out >= 0 && q.n_out <= h->S.n, "pixie_mpm_batch_run: scene %d: n_out %d (the scene has %d particles)", s, q.n_out, h->S.n);
+        if (q.n_out > 0) {
+            PX_REQUIRE(q.d_pos, "pixie_mpm_batch_run: scene %d: n_out %d with a null d_pos", s, q.n_out);
+            PX_REQUIRE(std::isfinite(q.scale) && q.scale != 0.0, "pixie_mpm_batch_run: scene %d: bad scale %g", s, q.scale);
         }
-        if (batch_issue_grid(b, gp, i, st)) return 1;
-        const bool last = (i == n_substeps - 1);
-        for (int s = 0; s < ns; ++s) {
-            pixie_mpm* h = b->h[s];
-            h->time = h->time + dt;  // mpm_solver_warp.py:637
-            const StepParams sp = make_params(h, dt, h->time);
-            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, true, !last, sp, st, pp[s])) return 1;
+        sc[s].dt = q.dt;
+        sc[s].chunk = q.steps_per_chunk;
+        sc[s].n_chunks = q.n_chunks;
+        sc[s].total = q.steps_per_chunk * q.n_chunks;
+        sc[s].exp = q.n_out > 0 && q.n_chunks > 0;
+        if (sc[s].exp) {
+            ex[s].X = make_frame_xform(q.shift, q.scale, q.mean, q.inv_rotation);
+            ex[s].init_cov = h->init_cov;
+            ex[s].pos = q.d_pos;
+            ex[s].cov = q.d_cov;
+            ex[s].n_out = q.n_out;
         }
-        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
     }
-    PX_CHECK_HIP(hipEventRecord(b->finished, st));
-    return 0;
+    for (int s = 0; s < ns; ++s)
+        if (batch_check_handle(b->h[s], s, "pixie_mpm_batch_run")) return 1;
+    int dev = -1;
+    PX_CHECK_HIP(hipGetDevice(&dev));
+    PX_REQUIRE(dev == b->device, "pixie_mpm_batch_run: HIP device %d is current, the batch was created on device %d", dev, b->device);
+    return batch_schedule(b, sc, ex, as_stream(stream));
 }
 
 int pixie_mpm_batch_destroy(pixie_mpm_batch* b) {
@@ -2742,10 +2937,7 @@ int pixie_mpm_export_frame(pixie_mpm* h, int n_out, const double shift[3], doubl
                            const double inv_rotation[9], float* d_pos, float* d_cov, void* stream) {
     PX_REQUIRE(h && shift && mean && inv_rotation && d_pos, "pixie_mpm_export_frame: null argument");
     PX_REQUIRE(n_out > 0 && n_out <= h->S.n && scale != 0.0, "pixie_mpm_export_frame: bad n_out / scale");
-    FrameXform X{};
-    for (int d = 0; d < 3; ++d) { X.shift[d] = (float)shift[d]; X.mean[d] = (float)mean[d]; }
-    X.inv_scale = (float)(1.0 / scale); X.inv_scale2 = (float)(1.0 / (scale * scale));
-    for (int c = 0; c < 9; ++c) X.M[c] = (float)inv_rotation[c];
+    const FrameXform X = make_frame_xform(shift, scale, mean, inv_rotation);
     hipLaunchKernelGGL(frame_export_kernel, dim3(cdiv(h->S.n, 256)), dim3(256), 0, as_stream(stream), h->S, h->init_cov, X, n_out, d_pos, d_cov);
     PX_CHECK_HIP(hipGetLastError());
     return 0;

@@ -20,6 +20,7 @@ Differences a caller can observe, by design:
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 
 import numpy as np
@@ -552,10 +553,7 @@ class MPM_Simulator_WARP:
         (pos_render (gs_num,3), cov3D_render (gs_num,6)) == (transform_to_original_coordinates(undoshift2center111(
         export_particle_x_to_torch()[:gs_num], z_shift), scale, mean, Rs), apply_inverse_cov_rotations(
         export_particle_cov_to_torch().view(-1,6)[:gs_num] / scale**2, Rs))."""
-        M = np.eye(3)
-        for R in reversed(list(rotation_matrices)):   # apply_inverse_rotations: p @ R_k, then @ R_{k-1}, ...
-            M = M @ np.asarray(R.detach().cpu() if torch.is_tensor(R) else R, dtype=np.float64)
-        mean = [float(v) for v in (original_mean_pos.detach().cpu() if torch.is_tensor(original_mean_pos) else original_mean_pos)]
+        M, mean = _frame_transform(original_mean_pos, rotation_matrices)
         pos = torch.empty((int(gs_num), 3), dtype=torch.float32, device=self.device)
         cov = torch.empty((int(gs_num), 6), dtype=torch.float32, device=self.device) if with_cov else None
         self.flush()
@@ -663,6 +661,28 @@ class MPM_Simulator_WARP:
                                                        start_time=start_time, end_time=(end_time / layers) * (k + 1))
 
 
+def _frame_transform(original_mean_pos, rotation_matrices):
+    """(M, mean) of the per-frame export: the rotation chain folded into one row-major matrix on the host, and the mean as floats"""
+    M = np.eye(3)
+    for R in reversed(list(rotation_matrices)):   # apply_inverse_rotations: p @ R_k, then @ R_{k-1}, ...
+        M = M @ np.asarray(R.detach().cpu() if torch.is_tensor(R) else R, dtype=np.float64)
+    mean = [float(v) for v in (original_mean_pos.detach().cpu() if torch.is_tensor(original_mean_pos) else original_mean_pos)]
+    return M, mean
+
+
+def _is_sequence(v):
+    """a per-scene argument of SceneBatch.run (a scalar otherwise)"""
+    if isinstance(v, (np.ndarray, torch.Tensor)):
+        return v.ndim > 0
+    return isinstance(v, (list, tuple, range))
+
+
+def _check_out(t, shape, device, what):
+    if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == torch.float32 and t.device == torch.device(device)
+            and t.is_contiguous()):
+        raise ValueError(f"SceneBatch.run_frames: out {what} must be a contiguous float32 tensor of shape {shape} on {device}")
+
+
 def run_batch(solvers, dt, n_substeps, streams=None):
     """Advance several INDEPENDENT scenes by `n_substeps` substeps each, concurrently on one GPU (no reference counterpart: the
     reference runs one scene per process, gs_simulation.py:633-634; BASELINE configs[3] is a batch of scenes).
@@ -717,6 +737,21 @@ def run_batch(solvers, dt, n_substeps, streams=None):
         raise errors[0]
 
 
+@dataclasses.dataclass
+class FrameSchedule:
+    """One scene's frame loop for `SceneBatch.run_frames` (gs_simulation.py:561,573-634): `n_frames` times, export the frame for the
+    rasteriser (the arguments of `export_frame_for_rendering`; gs_num 0: no export), then step `steps_per_frame` substeps of `dt`."""
+    dt: float
+    steps_per_frame: int
+    n_frames: int
+    gs_num: int = 0
+    scale_origin: float = 1.0
+    original_mean_pos: object = (0.0, 0.0, 0.0)
+    rotation_matrices: object = ()
+    z_shift_value: float = 0.0
+    with_cov: bool = True
+
+
 class SceneBatch:
     """Step several INDEPENDENT scenes with one launch pair per substep (no reference counterpart; C ABI pixie_mpm_batch_*).
 
@@ -728,12 +763,18 @@ class SceneBatch:
 
         with SceneBatch([a, b, c]) as batch:
             batch.run(dt, 200)
+            batch.run([1e-4, 2e-5, 1e-5], [400, 2000, 1000])       # per-scene dt and substep counts
+            frames = batch.run_frames([FrameSchedule(1e-4, 400, 25, gs_num=a.n_particles, ...), ...])
 
+    Scenes at different dt / counts share launches: substep j of every scene is the call's global step j, so a call issues
+    max_s(substeps_s) grid launches, and scenes that finish early drop out.  `run_frames` runs each scene's frame loop of
+    gs_simulation.py (export, then steps_per_frame substeps) with the exports of the scenes that start a frame at the same global
+    step in one launch; each scene ends -- state and frames -- in the bits of its solo loop.
     Limits (refused with ValueError / PixieHipError before anything runs):
       * 1 ... 32 distinct solvers, all on one device and all from the same library (product or diag=True);
       * per scene at most 16 boundary conditions and at most 8 particle modifiers (the cases `run` serves with extra launches);
       * no phase-API P2G pending; no `trace` set;
-      * one dt for all scenes per call.
+      * per-scene calls: dt > 0 and finite, counts >= 0, one entry per scene, gs_num <= the scene's particles.
     The solvers must outlive the batch, and `initialize()` replaces a solver's handle: a batch built before it refuses to run.
 
     Kernel variant: every scene keeps the block-kernel variant it runs alone (the variants round differently).  A 100 k scene has ~500
@@ -781,7 +822,68 @@ class SceneBatch:
         return list(self._solvers)
 
     def run(self, dt, n_substeps):
-        """Advance every scene by `n_substeps` substeps of `dt` on the current stream (asynchronous, like `run`)."""
+        """Advance every scene by `n_substeps` substeps of `dt` on the current stream (asynchronous, like `run`).  Either argument may
+        be a sequence with one entry per scene: scene s then ends exactly as `solver_s.run(dt_s, n_s)` alone leaves it (n_s == 0:
+        untouched)."""
+        if not (_is_sequence(dt) or _is_sequence(n_substeps)):
+            self._call("pixie_mpm_batch_step", float(dt), int(n_substeps))
+            return
+        dts, ns = self._per_scene(dt, "dt"), self._per_scene(n_substeps, "n_substeps")
+        arr = (_lib.BatchSched * len(self._solvers))()
+        for q, d, n in zip(arr, dts, ns):
+            q.dt, q.steps_per_chunk, q.n_chunks = float(d), int(n), 1
+        self._call("pixie_mpm_batch_run", arr, len(arr))
+
+    def run_frames(self, schedules, out=None):
+        """Each scene's frame loop (one FrameSchedule per scene), all on the current stream, asynchronously: returns per scene
+        (pos (n_frames, gs_num, 3), cov (n_frames, gs_num, 6) or None), bit-equal to the solo loop
+            for f in range(n_frames):
+                pos[f], cov[f] = s.export_frame_for_rendering(gs_num, scale_origin, original_mean_pos, rotation_matrices,
+                                                              z_shift_value, with_cov)
+                s.run(dt, steps_per_frame)
+        `out`: one preallocated (pos, cov) pair per scene (float32, contiguous, on the batch's device; cov None without with_cov)."""
+        schedules = list(schedules)
+        if len(schedules) != len(self._solvers):
+            raise ValueError(f"SceneBatch.run_frames: {len(schedules)} schedules for {len(self._solvers)} scenes")
+        if out is not None and len(out) != len(self._solvers):
+            raise ValueError(f"SceneBatch.run_frames: {len(out)} output pairs for {len(self._solvers)} scenes")
+        arr = (_lib.BatchSched * len(schedules))()
+        results = []
+        for i, (q, c) in enumerate(zip(schedules, arr)):
+            nf, gs = int(q.n_frames), int(q.gs_num)
+            c.dt, c.steps_per_chunk, c.n_chunks, c.n_out = float(q.dt), int(q.steps_per_frame), nf, gs
+            shape = (max(nf, 0), max(gs, 0))
+            if out is not None:
+                pos, cov = out[i]
+                _check_out(pos, shape + (3,), self.device, f"scene {i} pos")
+                if q.with_cov:
+                    _check_out(cov, shape + (6,), self.device, f"scene {i} cov")
+                else:
+                    cov = None
+            else:
+                pos = torch.empty(shape + (3,), dtype=torch.float32, device=self.device)
+                cov = torch.empty(shape + (6,), dtype=torch.float32, device=self.device) if q.with_cov else None
+            results.append((pos, cov))
+            if gs > 0:
+                M, mean = _frame_transform(q.original_mean_pos, q.rotation_matrices)
+                c.shift[:] = [1.0, 1.0, 1.0 + float(q.z_shift_value)]
+                c.scale = float(q.scale_origin)
+                c.mean[:] = mean
+                c.inv_rotation[:] = [float(v) for v in M.reshape(-1)]
+                c.d_pos = pos.data_ptr() if pos.numel() else None
+                c.d_cov = cov.data_ptr() if cov is not None and cov.numel() else None
+        self._call("pixie_mpm_batch_run", arr, len(arr))
+        return results
+
+    def _per_scene(self, v, what):
+        if not _is_sequence(v):
+            return [v] * len(self._solvers)
+        v = list(v)
+        if len(v) != len(self._solvers):
+            raise ValueError(f"SceneBatch.run: {len(v)} values of {what} for {len(self._solvers)} scenes")
+        return v
+
+    def _call(self, name, *args):
         if self._b is None:
             raise _lib.PixieHipError("SceneBatch: closed")
         for s, h in zip(self._solvers, self._handles):
@@ -790,8 +892,7 @@ class SceneBatch:
         for s in self._solvers:
             s.flush()      # deferred p2g2p() substeps; orders the current stream after them
         with torch.cuda.device(self.device):  # (the caller's current device is left as it was)
-            check(self._L.pixie_mpm_batch_step(self._b, float(dt), int(n_substeps), _lib.current_stream_ptr()), "pixie_mpm_batch_step",
-                  lib=self._L)
+            check(getattr(self._L, name)(self._b, *args, _lib.current_stream_ptr()), name, lib=self._L)
         for s in self._solvers:
             s._warn_if_particles_lost()
             if s.live_exports:

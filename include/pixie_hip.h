@@ -163,6 +163,17 @@ typedef struct pixie_batch_sched {
 int pixie_mpm_batch_create(pixie_mpm_batch** out, pixie_mpm* const* handles, int n_handles);
 int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* stream);
 int pixie_mpm_batch_run(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, int n_scenes, void* stream);
+/* pixie_mpm_batch_run with 3DGS splats: a scene s with splats[s] set exports, per frame, (pos, cov) and the log-scales and
+ * quaternions of pixie_mpm_export_frame_splats, bit for bit as that call in its solo loop.  At an export step the scenes without
+ * splats keep pixie_mpm_batch_run's export launch and those with splats share a second one.  splats == NULL, or every entry
+ * {NULL, NULL}: exactly pixie_mpm_batch_run's launches.  Refused before anything runs: only one of the two pointers set, splats
+ * with n_out == 0 or with a null d_cov. */
+typedef struct pixie_batch_splat_out {
+    float* d_log_scale;                /* [n_chunks][n_out][3] or NULL */
+    float* d_quat;                     /* [n_chunks][n_out][4] (wxyz) or NULL */
+} pixie_batch_splat_out;
+int pixie_mpm_batch_run_splats(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, const pixie_batch_splat_out* splats /* [n_scenes] or NULL */,
+                               int n_scenes, void* stream);
 int pixie_mpm_batch_destroy(pixie_mpm_batch* b);
 
 /* compute_cov_from_F (mpm_utils.py:529-553) and compute_R_from_F (:556-580) as used by
@@ -177,6 +188,18 @@ int pixie_mpm_export_R(pixie_mpm* h, float* d_R /* [n][9] */, void* stream);
 int pixie_mpm_export_frame(pixie_mpm* h, int n_out, const double shift[3], double scale, const double mean[3],
                            const double inv_rotation[9], float* d_pos /* [n_out][3] */, float* d_cov /* [n_out][6] or NULL */,
                            void* stream);
+/* 3DGS splat parameters of a covariance (cov3D_to_log_scales_and_quats, PG/gs_simulation.py:253-288): per row of d_cov
+ * (s11, s12, s13, s22, s23, s33), the eigenvalues in descending order as log_scale = 0.5 log(max(lambda, 1e-12)) and the
+ * eigenvector matrix R (columns) as a unit quaternion (w, x, y, z), w >= 0.  R's signs are fixed: columns 0 and 1 have their
+ * largest-magnitude component positive, column 2 = col0 x col1 (right-handed).  Double-precision Jacobi inside.  n == 0 is a
+ * no-op; n < 0 and null pointers are refused.  One launch. */
+int pixie_splat_from_cov(const float* d_cov /* [n][6] */, int64_t n, float* d_log_scale /* [n][3] */, float* d_quat /* [n][4] wxyz */,
+                         void* stream);
+/* pixie_mpm_export_frame with the splats of the exported covariances (the per-frame PLY of PG/gs_simulation.py:290-322) in the same
+ * launch: d_log_scale / d_quat are the bits pixie_splat_from_cov gives for d_cov.  Every output is required. */
+int pixie_mpm_export_frame_splats(pixie_mpm* h, int n_out, const double shift[3], double scale, const double mean[3],
+                                  const double inv_rotation[9], float* d_pos /* [n_out][3] */, float* d_cov /* [n_out][6] */,
+                                  float* d_log_scale /* [n_out][3] */, float* d_quat /* [n_out][4] */, void* stream);
 /* Particles whose 3x3x3 stencil left the grid (undefined behaviour in the reference).  Here such a particle is frozen
  * (selection <- 2: it neither moves nor scatters mass again) and counted ONCE; slow-path particles that drifted out of
  * every active block between two re-binnings are dropped from that substep's P2G and counted too.  Synchronises

@@ -73,6 +73,11 @@ class BatchSched(C.Structure):
                 ("d_pos", C.c_void_p), ("d_cov", C.c_void_p)]
 
 
+class BatchSplatOut(C.Structure):
+    """struct pixie_batch_splat_out"""
+    _fields_ = [("d_log_scale", C.c_void_p), ("d_quat", C.c_void_p)]
+
+
 class FieldDesc(C.Structure):
     """struct pixie_field_desc"""
     _fields_ = [("d_pred", C.c_void_p), ("d_mask", C.c_void_p),
@@ -111,6 +116,9 @@ SIGNATURES = {
     "pixie_mpm_batch_create": (_I, [C.POINTER(_VP), C.POINTER(_VP), _I]),
     "pixie_mpm_batch_step": (_I, [_VP, _D, _I, _VP]),
     "pixie_mpm_batch_run": (_I, [_VP, C.POINTER(BatchSched), _I, _VP]),
+    "pixie_mpm_batch_run_splats": (_I, [_VP, C.POINTER(BatchSched), C.POINTER(BatchSplatOut), _I, _VP]),
+    "pixie_splat_from_cov": (_I, [_VP, _I64, _VP, _VP, _VP]),
+    "pixie_mpm_export_frame_splats": (_I, [_VP, _I, _D3, _D, _D3, C.POINTER(C.c_double), _VP, _VP, _VP, _VP, _VP]),
     "pixie_mpm_batch_destroy": (_I, [_VP]),
     "pixie_pack_fields": (_I, [_VP, _VP, _I64, _I64, _VP, _I64, _VP]),
     "pixie_conv_cout_padded": (_I, [_I]),

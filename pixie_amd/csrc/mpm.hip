@@ -40,6 +40,7 @@
 #include "../../include/pixie_hip.h"
 #include "common.h"
 #include "mpm_math.h"
+#include "splat_math.h"
 
 namespace pixie {
 
@@ -1499,6 +1500,57 @@ __global__ void frame_export_batch_kernel(ExportLaunch L) {
     const int i = ((int)blockIdx.x - L.first[k]) * 256 + (int)threadIdx.x;
 #include "frame_export_body.h"
 }
+// The frame export with the 3DGS splat parameters of every exported covariance (PG/gs_simulation.py:290-322, the per-frame PLY):
+// frame_export_kernel's body, then splat::splat_from_cov of the covariance it has just stored (Rr, the values written to cov_out),
+// so the splats are the bits pixie_splat_from_cov gives for that cov.  Needs cov_out (the host refuses NULL).
+__global__ void frame_splat_kernel(MpmPtrs S, const float* __restrict__ init_cov, FrameXform X, int n_out, float* __restrict__ pos_out,
+                                   float* __restrict__ cov_out, float* __restrict__ log_scale_out, float* __restrict__ quat_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+#include "frame_export_body.h"
+    const float cs[6] = {Rr.m[0], Rr.m[1], Rr.m[2], Rr.m[4], Rr.m[5], Rr.m[8]};
+    float ls[3], qt[4];
+    splat::splat_from_cov(cs, ls, qt);
+    for (int d = 0; d < 3; ++d) log_scale_out[(size_t)s * 3 + d] = ls[d];
+    for (int d = 0; d < 4; ++d) quat_out[(size_t)s * 4 + d] = qt[d];
+}
+// Splat outputs of one scene in a pixie_mpm_batch_run_splats call: a record array of its own in the call's table, beside the
+// BatchExport records (indexed alike: descriptor s -> sp[s]).
+struct BatchSplat {
+    float* log_scale;              // frame 0 of [n_frames][n_out][3]
+    float* quat;                   // frame 0 of [n_frames][n_out][4]
+};
+// frame_export_batch_kernel's twin for the scenes that export splats (the same ExportLaunch, listing only those scenes)
+__global__ void frame_splat_batch_kernel(ExportLaunch L, const BatchSplat* __restrict__ sp) {
+    const int k = batch_scene_of(L, (int)blockIdx.x);
+    const MpmPtrs S = batch_desc(L, k).S;
+    const BatchExport E = const_view(L.ex + L.scene[k]);
+    const BatchSplat P = const_view(sp + L.scene[k]);
+    const FrameXform X = E.X;
+    const float* __restrict__ init_cov = E.init_cov;
+    const int n_out = E.n_out;
+    float* __restrict__ pos_out = E.pos + (size_t)L.frame[k] * (size_t)n_out * 3;
+    float* __restrict__ cov_out = E.cov + (size_t)L.frame[k] * (size_t)n_out * 6;
+    float* __restrict__ log_scale_out = P.log_scale + (size_t)L.frame[k] * (size_t)n_out * 3;
+    float* __restrict__ quat_out = P.quat + (size_t)L.frame[k] * (size_t)n_out * 4;
+    const int i = ((int)blockIdx.x - L.first[k]) * 256 + (int)threadIdx.x;
+#include "frame_export_body.h"
+    const float cs[6] = {Rr.m[0], Rr.m[1], Rr.m[2], Rr.m[4], Rr.m[5], Rr.m[8]};
+    float ls[3], qt[4];
+    splat::splat_from_cov(cs, ls, qt);
+    for (int d = 0; d < 3; ++d) log_scale_out[(size_t)s * 3 + d] = ls[d];
+    for (int d = 0; d < 4; ++d) quat_out[(size_t)s * 4 + d] = qt[d];
+}
+// cov3D_to_log_scales_and_quats (PG/gs_simulation.py:253-288) on its own: [n][6] -> [n][3], [n][4] (wxyz)
+__global__ void splat_from_cov_kernel(const float* __restrict__ cov, long n, float* __restrict__ log_scale_out, float* __restrict__ quat_out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float cs[6];
+    for (int d = 0; d < 6; ++d) cs[d] = cov[i * 6 + d];
+    float ls[3], qt[4];
+    splat::splat_from_cov(cs, ls, qt);
+    for (int d = 0; d < 3; ++d) log_scale_out[i * 3 + d] = ls[d];
+    for (int d = 0; d < 4; ++d) quat_out[i * 4 + d] = qt[d];
+}
 // compute_R_from_F, mpm_utils.py:556-580 (stores R^T)
 __global__ void rot_kernel(MpmPtrs S, float* __restrict__ Rout, const int* perm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2101,6 +2153,7 @@ struct pixie_mpm_batch {
     size_t cap = 0;
     std::vector<size_t> sp_off;              // this window's StepParams table of scene s, in d_tab / h_tab
     size_t ex_off = 0;                       // this call's export records (BatchExport per scene), if it exports
+    size_t spl_off = 0;                      // this call's splat records (BatchSplat per scene), if a scene exports splats
     hipEvent_t ev_up[2] = {nullptr, nullptr};      // after the last copy out of h_buf[i] (h_buf[i] is rewritten only once it has run)
     int cur_buf = 1;
     int device = 0;                          // the HIP device current at creation: the events and tables live there
@@ -2143,8 +2196,10 @@ constexpr int kBatchWindow = 1024;
 // host by running the solo step's own time / BC bookkeeping (make_params, make_bcset, advance_bcs_state) ahead on copies of the
 // handle's state, which the plans of the steps before g0 have brought to global step g0, and uploaded in one copy.  Launches index
 // the tables with the step relative to g0.  The plan of every substep checks what it computes against these tables (batch_expect_*).
-// `ex`: the call's export records, uploaded with every window (NULL: the call does not export).
-int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, const std::vector<BatchExport>* ex, hipStream_t st) {
+// `ex`: the call's export records, uploaded with every window (NULL: the call does not export); `spl` likewise its splat records
+// (NULL: no scene exports splats).
+int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, const std::vector<BatchExport>* ex,
+                 const std::vector<BatchSplat>* spl, hipStream_t st) {
     const int ns = (int)b->h.size();
     std::vector<size_t> bc_off(ns), bc_stride(ns);
     std::vector<int> n_win(ns);
@@ -2169,6 +2224,11 @@ int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, 
     if (ex) {
         ex_off = off = align_up(off, 16);
         off += (size_t)ns * sizeof(BatchExport);
+    }
+    size_t spl_off = 0;
+    if (spl) {
+        spl_off = off = align_up(off, 16);
+        off += (size_t)ns * sizeof(BatchSplat);
     }
     // Rewriting d_tab between the windows of a call is safe without a synchronisation: the copy below is issued on `st`, the stream
     // of every launch of the call, after the last launch of the previous window, and a launch of this window is issued after it.
@@ -2223,6 +2283,8 @@ int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, 
     }
     b->ex_off = ex_off;
     if (ex) memcpy(b->h_tab + ex_off, ex->data(), (size_t)ns * sizeof(BatchExport));
+    b->spl_off = spl_off;
+    if (spl) memcpy(b->h_tab + spl_off, spl->data(), (size_t)ns * sizeof(BatchSplat));
     PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, off, hipMemcpyHostToDevice, st));
     PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
     return 0;
@@ -2350,26 +2412,33 @@ int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, const 
     return 0;
 }
 
-// One frame_export_batch_kernel launch for every scene with frame[s] >= 0 (the frame it exports); none if there is none.
-int batch_issue_export(pixie_mpm_batch* b, const std::vector<int>& frame, hipStream_t st) {
+// One frame_export_batch_kernel launch for every scene with frame[s] >= 0 (the frame it exports) and no splats, and one
+// frame_splat_batch_kernel launch for those with splats (splat[s]; empty: none has); none for an empty list.
+int batch_issue_export(pixie_mpm_batch* b, const std::vector<int>& frame, const std::vector<char>& splat, hipStream_t st) {
     const int ns = (int)b->h.size();
-    ExportLaunch L;
-    memset(&L, 0, sizeof L);
-    L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
-    L.ex = reinterpret_cast<const BatchExport*>(b->d_tab + b->ex_off);
-    long total = 0;
-    for (int s = 0; s < ns; ++s) {
-        if (frame[s] < 0) continue;
-        L.scene[L.n] = s;
-        L.frame[L.n] = frame[s];
+    for (int with_splat = 0; with_splat < (splat.empty() ? 1 : 2); ++with_splat) {
+        ExportLaunch L;
+        memset(&L, 0, sizeof L);
+        L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
+        L.ex = reinterpret_cast<const BatchExport*>(b->d_tab + b->ex_off);
+        long total = 0;
+        for (int s = 0; s < ns; ++s) {
+            if (frame[s] < 0 || (!splat.empty() && (splat[s] != 0) != (with_splat != 0))) continue;
+            L.scene[L.n] = s;
+            L.frame[L.n] = frame[s];
+            L.first[L.n] = (int)total;
+            total += cdiv(b->h[s]->S.n, 256);
+            ++L.n;
+        }
+        if (L.n == 0) continue;
         L.first[L.n] = (int)total;
-        total += cdiv(b->h[s]->S.n, 256);
-        ++L.n;
+        if (with_splat)
+            hipLaunchKernelGGL(frame_splat_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L,
+                               reinterpret_cast<const BatchSplat*>(b->d_tab + b->spl_off));
+        else
+            hipLaunchKernelGGL(frame_export_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L);
+        PX_CHECK_HIP(hipGetLastError());
     }
-    if (L.n == 0) return 0;
-    L.first[L.n] = (int)total;
-    hipLaunchKernelGGL(frame_export_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L);
-    PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2381,15 +2450,22 @@ int batch_issue_export(pixie_mpm_batch* b, const std::vector<int>& frame, hipStr
 // frame_export reads F_trial -- and then plans and issues its next chunk's P2G-only launch, so that it joins the next grid launch.
 // Frame 0's export precedes everything.  Chunk boundaries are kept as given: each scene sees exactly the pixie_mpm_step calls
 // (and exports) of its solo loop, in the same order, on its own host state.
-int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const std::vector<BatchExport>& ex, hipStream_t st) {
+// `spl`: per scene, where its splats go (BatchSplat, NULL pointers: none); empty when no scene exports splats.
+int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const std::vector<BatchExport>& ex,
+                   const std::vector<BatchSplat>& spl, hipStream_t st) {
     const int ns = (int)b->h.size();
     int G = 0;
     bool any_ex = false;
     for (const BatchSched& q : sc) { G = std::max(G, q.total); any_ex = any_ex || q.exp; }
     if (G == 0 && !any_ex) return 0;
     const std::vector<BatchExport>* exr = any_ex ? &ex : nullptr;
+    std::vector<char> splat;               // which exporting scenes go through frame_splat_batch_kernel (empty: none)
+    for (int s = 0; s < (int)spl.size(); ++s)
+        if (sc[s].exp && spl[s].log_scale) { splat.assign(ns, 0); break; }
+    for (int s = 0; s < (int)splat.size(); ++s) splat[s] = sc[s].exp && spl[s].log_scale;
+    const std::vector<BatchSplat>* splr = splat.empty() ? nullptr : &spl;
     int g0 = 0;
-    if (batch_upload(b, sc, g0, exr, st)) return 1;
+    if (batch_upload(b, sc, g0, exr, splr, st)) return 1;
     std::vector<ParticlePlan> pp(ns);
     std::vector<GridPlan> gp(ns);
     std::vector<char> on(ns, 0), next(ns, 0);
@@ -2403,7 +2479,7 @@ int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const 
             any = any || e;
         }
         if (!any) break;
-        if (batch_issue_export(b, frame, st)) return 1;
+        if (batch_issue_export(b, frame, splat, st)) return 1;
     }
     // substep 0 of the first chunk: modifiers + stress + P2G at time t0
     for (int s = 0; s < ns; ++s) {
@@ -2417,7 +2493,7 @@ int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const 
     for (int g = 0; g < G; ++g) {
         if (g - g0 == kBatchWindow) {
             g0 = g;
-            if (batch_upload(b, sc, g0, exr, st)) return 1;
+            if (batch_upload(b, sc, g0, exr, splr, st)) return 1;
         }
         const int i = g - g0;
         for (int s = 0; s < ns; ++s) {
@@ -2448,7 +2524,7 @@ int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const 
         if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
         if (!any_next) continue;
         // scenes between two chunks: the next frame's export, then the next chunk's P2G-only launch at the same time
-        if (batch_issue_export(b, frame, st)) return 1;
+        if (batch_issue_export(b, frame, splat, st)) return 1;
         for (int s = 0; s < ns; ++s) {
             pp[s].run = false;
             if (!next[s]) continue;
@@ -2845,19 +2921,27 @@ int pixie_mpm_batch_step(pixie_mpm_batch* b, double dt, int n_substeps, void* st
     // one chunk of n_substeps for every scene: the launches of the scheduler's common case
     BatchSched q;
     q.dt = dt; q.chunk = n_substeps; q.n_chunks = 1; q.total = n_substeps;
-    return batch_schedule(b, std::vector<BatchSched>(ns, q), std::vector<BatchExport>(), as_stream(stream));
+    return batch_schedule(b, std::vector<BatchSched>(ns, q), std::vector<BatchExport>(), std::vector<BatchSplat>(), as_stream(stream));
 }
 
 // Per-scene dt, substep counts and frame exports: each scene s runs, bit for bit, its solo frame loop
 //   for f < n_chunks: [pixie_mpm_export_frame(frame f) if n_out > 0]; pixie_mpm_step(dt, steps_per_chunk)
 // with the launches shared across scenes (batch_schedule).
 int pixie_mpm_batch_run(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, int n_scenes, void* stream) {
+    return pixie_mpm_batch_run_splats(b, per_scene, nullptr, n_scenes, stream);
+}
+
+// pixie_mpm_batch_run, with the scenes that have splats[s] set exporting (pos, cov, log-scales, quaternions) per frame, bit for
+// bit as pixie_mpm_export_frame_splats in their solo loop.  splats == NULL, or no scene with splats: pixie_mpm_batch_run's launches.
+int pixie_mpm_batch_run_splats(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, const pixie_batch_splat_out* splats, int n_scenes,
+                               void* stream) {
     PX_REQUIRE(b && per_scene, "pixie_mpm_batch_run: null argument");
     const int ns = (int)b->h.size();
     PX_REQUIRE(n_scenes == ns, "pixie_mpm_batch_run: %d schedules for a batch of %d scenes", n_scenes, ns);
     std::vector<BatchSched> sc(ns);
     std::vector<BatchExport> ex(ns);
     memset(ex.data(), 0, ex.size() * sizeof(BatchExport));
+    std::vector<BatchSplat> spl(ns, BatchSplat{nullptr, nullptr});
     for (int s = 0; s < ns; ++s) {
         const pixie_batch_sched& q = per_scene[s];
         const pixie_mpm* h = b->h[s];
@@ -2883,13 +2967,21 @@ int pixie_mpm_batch_run(pixie_mpm_batch* b, const pixie_batch_sched* per_scene, 
             ex[s].cov = q.d_cov;
             ex[s].n_out = q.n_out;
         }
+        if (splats && (splats[s].d_log_scale || splats[s].d_quat)) {
+            const pixie_batch_splat_out& o = splats[s];
+            PX_REQUIRE(o.d_log_scale && o.d_quat, "pixie_mpm_batch_run_splats: scene %d: only one of d_log_scale / d_quat is set", s);
+            PX_REQUIRE(q.n_out > 0, "pixie_mpm_batch_run_splats: scene %d: splat outputs with n_out 0 (nothing is exported)", s);
+            PX_REQUIRE(q.d_cov, "pixie_mpm_batch_run_splats: scene %d: splat outputs need d_cov (the splats are decomposed covariances)", s);
+            spl[s].log_scale = o.d_log_scale;
+            spl[s].quat = o.d_quat;
+        }
     }
     for (int s = 0; s < ns; ++s)
         if (batch_check_handle(b->h[s], s, "pixie_mpm_batch_run")) return 1;
     int dev = -1;
     PX_CHECK_HIP(hipGetDevice(&dev));
     PX_REQUIRE(dev == b->device, "pixie_mpm_batch_run: HIP device %d is current, the batch was created on device %d", dev, b->device);
-    return batch_schedule(b, sc, ex, as_stream(stream));
+    return batch_schedule(b, sc, ex, spl, as_stream(stream));
 }
 
 int pixie_mpm_batch_destroy(pixie_mpm_batch* b) {
@@ -2939,6 +3031,28 @@ int pixie_mpm_export_frame(pixie_mpm* h, int n_out, const double shift[3], doubl
     PX_REQUIRE(n_out > 0 && n_out <= h->S.n && scale != 0.0, "pixie_mpm_export_frame: bad n_out / scale");
     const FrameXform X = make_frame_xform(shift, scale, mean, inv_rotation);
     hipLaunchKernelGGL(frame_export_kernel, dim3(cdiv(h->S.n, 256)), dim3(256), 0, as_stream(stream), h->S, h->init_cov, X, n_out, d_pos, d_cov);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int pixie_mpm_export_frame_splats(pixie_mpm* h, int n_out, const double shift[3], double scale, const double mean[3],
+                                  const double inv_rotation[9], float* d_pos, float* d_cov, float* d_log_scale, float* d_quat, void* stream) {
+    PX_REQUIRE(h && shift && mean && inv_rotation, "pixie_mpm_export_frame_splats: null argument");
+    PX_REQUIRE(n_out > 0 && n_out <= h->S.n && scale != 0.0, "pixie_mpm_export_frame_splats: bad n_out %d / scale %g", n_out, scale);
+    PX_REQUIRE(d_pos && d_cov && d_log_scale && d_quat, "pixie_mpm_export_frame_splats: null output (d_pos, d_cov, d_log_scale and d_quat are all required)");
+    const FrameXform X = make_frame_xform(shift, scale, mean, inv_rotation);
+    hipLaunchKernelGGL(frame_splat_kernel, dim3(cdiv(h->S.n, 256)), dim3(256), 0, as_stream(stream), h->S, h->init_cov, X, n_out, d_pos, d_cov,
+                       d_log_scale, d_quat);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int pixie_splat_from_cov(const float* d_cov, int64_t n, float* d_log_scale, float* d_quat, void* stream) {
+    PX_REQUIRE(n >= 0, "pixie_splat_from_cov: n %lld < 0", (long long)n);
+    if (n == 0) return 0;
+    PX_REQUIRE(d_cov && d_log_scale && d_quat, "pixie_splat_from_cov: null pointer (d_cov, d_log_scale and d_quat are all required)");
+    PX_REQUIRE(n <= (int64_t)INT_MAX * 256, "pixie_splat_from_cov: n %lld exceeds one launch", (long long)n);
+    hipLaunchKernelGGL(splat_from_cov_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), d_cov, (long)n, d_log_scale, d_quat);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -562,6 +562,24 @@ class MPM_Simulator_WARP:
                                                  C.c_void_p(cov.data_ptr()) if with_cov else None, self._stream), "export_frame")
         return pos, cov
 
+    def export_frame_splats(self, gs_num, scale_origin, original_mean_pos, rotation_matrices, z_shift_value=0.0):
+        """`export_frame_for_rendering` plus the 3DGS splat parameters of every exported covariance, in ONE launch: returns
+        (pos (gs_num,3), cov (gs_num,6), log_scales (gs_num,3), quats_wxyz (gs_num,4)), pos / cov bit-equal to
+        export_frame_for_rendering's and (log_scales, quats) to splat_export.cov3D_to_log_scales_and_quats(cov) -- what
+        export_gaussians_to_ply (gs_simulation.py:290-322) writes per frame."""
+        M, mean = _frame_transform(original_mean_pos, rotation_matrices)
+        n = int(gs_num)
+        pos = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        cov = torch.empty((n, 6), dtype=torch.float32, device=self.device)
+        ls = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        quat = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        self.flush()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        self._check(self._L.pixie_mpm_export_frame_splats(self._h, n, d3([1.0, 1.0, 1.0 + float(z_shift_value)]), float(scale_origin),
+                                                        d3(mean), (C.c_double * 9)(*M.reshape(-1)), ptr(pos), ptr(cov), ptr(ls),
+                                                        ptr(quat), self._stream), "export_frame_splats")
+        return pos, cov, ls, quat
+
     def print_time_profile(self):
         """:743-746"""
         print("MPM Time profile:")
@@ -740,7 +758,8 @@ def run_batch(solvers, dt, n_substeps, streams=None):
 @dataclasses.dataclass
 class FrameSchedule:
     """One scene's frame loop for `SceneBatch.run_frames` (gs_simulation.py:561,573-634): `n_frames` times, export the frame for the
-    rasteriser (the arguments of `export_frame_for_rendering`; gs_num 0: no export), then step `steps_per_frame` substeps of `dt`."""
+    rasteriser (the arguments of `export_frame_for_rendering`; gs_num 0: no export), then step `steps_per_frame` substeps of `dt`.
+    `with_splats`: export the frame as `export_frame_splats` does (pos, cov, log-scales, quaternions); implies the covariance."""
     dt: float
     steps_per_frame: int
     n_frames: int
@@ -750,6 +769,7 @@ class FrameSchedule:
     rotation_matrices: object = ()
     z_shift_value: float = 0.0
     with_cov: bool = True
+    with_splats: bool = False
 
 
 class SceneBatch:
@@ -841,29 +861,48 @@ class SceneBatch:
                 pos[f], cov[f] = s.export_frame_for_rendering(gs_num, scale_origin, original_mean_pos, rotation_matrices,
                                                               z_shift_value, with_cov)
                 s.run(dt, steps_per_frame)
-        `out`: one preallocated (pos, cov) pair per scene (float32, contiguous, on the batch's device; cov None without with_cov)."""
+        A scene with `with_splats` returns (pos, cov, log_scales (n_frames, gs_num, 3), quats_wxyz (n_frames, gs_num, 4)) instead,
+        each frame bit-equal to `export_frame_splats` in the solo loop; at an export step those scenes share one launch and the
+        others keep theirs.
+        `out`: one preallocated (pos, cov) pair per scene (float32, contiguous, on the batch's device; cov None without with_cov),
+        or a (pos, cov, log_scales, quats) 4-tuple for a scene with `with_splats`."""
         schedules = list(schedules)
         if len(schedules) != len(self._solvers):
             raise ValueError(f"SceneBatch.run_frames: {len(schedules)} schedules for {len(self._solvers)} scenes")
         if out is not None and len(out) != len(self._solvers):
             raise ValueError(f"SceneBatch.run_frames: {len(out)} output pairs for {len(self._solvers)} scenes")
         arr = (_lib.BatchSched * len(schedules))()
+        splats = (_lib.BatchSplatOut * len(schedules))()
         results = []
         for i, (q, c) in enumerate(zip(schedules, arr)):
             nf, gs = int(q.n_frames), int(q.gs_num)
             c.dt, c.steps_per_chunk, c.n_chunks, c.n_out = float(q.dt), int(q.steps_per_frame), nf, gs
             shape = (max(nf, 0), max(gs, 0))
+            with_cov = bool(q.with_cov or q.with_splats)
+            ls = quat = None
             if out is not None:
-                pos, cov = out[i]
+                if q.with_splats:
+                    if len(out[i]) != 4:
+                        raise ValueError(f"SceneBatch.run_frames: scene {i} has with_splats: out must be a (pos, cov, log_scales, quats) 4-tuple")
+                    pos, cov, ls, quat = out[i]
+                    _check_out(ls, shape + (3,), self.device, f"scene {i} log_scales")
+                    _check_out(quat, shape + (4,), self.device, f"scene {i} quats")
+                else:
+                    pos, cov = out[i]
                 _check_out(pos, shape + (3,), self.device, f"scene {i} pos")
-                if q.with_cov:
+                if with_cov:
                     _check_out(cov, shape + (6,), self.device, f"scene {i} cov")
                 else:
                     cov = None
             else:
                 pos = torch.empty(shape + (3,), dtype=torch.float32, device=self.device)
-                cov = torch.empty(shape + (6,), dtype=torch.float32, device=self.device) if q.with_cov else None
-            results.append((pos, cov))
+                cov = torch.empty(shape + (6,), dtype=torch.float32, device=self.device) if with_cov else None
+                if q.with_splats:
+                    ls = torch.empty(shape + (3,), dtype=torch.float32, device=self.device)
+                    quat = torch.empty(shape + (4,), dtype=torch.float32, device=self.device)
+            results.append((pos, cov, ls, quat) if q.with_splats else (pos, cov))
+            if q.with_splats and gs > 0 and nf > 0:
+                splats[i].d_log_scale, splats[i].d_quat = ls.data_ptr(), quat.data_ptr()
             if gs > 0:
                 M, mean = _frame_transform(q.original_mean_pos, q.rotation_matrices)
                 c.shift[:] = [1.0, 1.0, 1.0 + float(q.z_shift_value)]
@@ -872,7 +911,10 @@ class SceneBatch:
                 c.inv_rotation[:] = [float(v) for v in M.reshape(-1)]
                 c.d_pos = pos.data_ptr() if pos.numel() else None
                 c.d_cov = cov.data_ptr() if cov is not None and cov.numel() else None
-        self._call("pixie_mpm_batch_run", arr, len(arr))
+        if any(q.with_splats for q in schedules):
+            self._call("pixie_mpm_batch_run_splats", arr, splats, len(arr))
+        else:
+            self._call("pixie_mpm_batch_run", arr, len(arr))
         return results
 
     def _per_scene(self, v, what):

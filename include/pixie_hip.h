@@ -272,6 +272,13 @@ typedef struct pixie_conv_desc {
     const float* d_skip_in1; int32_t skip_c1;
     const void* d_skip_w16; const float* d_skip_bias;
     const uint32_t* d_skip_amax0; const uint32_t* d_skip_amax1;
+    /* f16x3 path only: 1 = d_w16 comes from pixie_conv_pack_weights_subpixel and the launch is the sub-pixel form of a 3^3
+     * convolution behind a nearest x2 upsampling (upsample = 1, ksize = 3, stride = 1; no folded skip): per output parity a
+     * 2x2x2 convolution over the stored tensor with pre-summed weights, 8 taps instead of 27.  Same prologue, crop,
+     * residual, statistics and split-K as the 27-tap form; results differ from it only by the summation order.  The
+     * size queries above follow this field.  The prologue runs on the stored tensor before the upsampling, so d_gamma / d_beta,
+     * refused with upsample = 1 otherwise, are allowed here and are [in_d][in_h][in_w]. */
+    int32_t w16_subpixel;
 } pixie_conv_desc;
 
 /* Repack an nn.Conv3d / nn.Conv1d weight (c_out, c_in, k,k,k) into the kernel's
@@ -282,6 +289,11 @@ int pixie_conv_pack_weights(const float* d_w_oidhw, float* d_w_packed, int c_out
  * |w|max) and swizzled for the f16 MFMA A operand; d_packed needs pixie_conv_packed16_bytes() bytes. */
 int64_t pixie_conv_packed16_bytes(int c_out, int c_in, int ksize);
 int pixie_conv_pack_weights_f16x2(const float* d_w_oidhw, void* d_packed, int c_out, int c_in, int ksize, void* stream);
+/* Sub-pixel packing of a 3^3 weight (c_out, c_in, 3,3,3) for pixie_conv_desc.w16_subpixel: the taps that read the same stored
+ * voxel after a nearest x2 upsampling are summed in fp32 per output parity, then scaled by |summed w|max and split as above,
+ * [parity 8][tap 8][c_in/8][c_out_padded].  pixie_conv_subpixel_bytes is 0 where the path does not apply (c_in % 16 != 0). */
+int64_t pixie_conv_subpixel_bytes(int c_out, int c_in);
+int pixie_conv_pack_weights_subpixel(const float* d_w_oidhw, void* d_packed, int c_out, int c_in, void* stream);
 /* F.conv3d / nn.Conv3d forward: exact-fp32 MFMA path (d_w), or the f16x3 split path (d_w16). */
 int pixie_conv3d_forward(const pixie_conv_desc* desc, void* stream);
 /* Epilogue statistics of the f16x3 path: buffer size in floats for desc->d_out_stats (0: layer not on that path), and

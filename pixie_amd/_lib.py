@@ -55,7 +55,8 @@ class ConvDesc(C.Structure):
                 ("d_skip_in0", C.c_void_p), ("skip_c0", C.c_int32),
                 ("d_skip_in1", C.c_void_p), ("skip_c1", C.c_int32),
                 ("d_skip_w16", C.c_void_p), ("d_skip_bias", C.c_void_p),
-                ("d_skip_amax0", C.c_void_p), ("d_skip_amax1", C.c_void_p)]
+                ("d_skip_amax0", C.c_void_p), ("d_skip_amax1", C.c_void_p),
+                ("w16_subpixel", C.c_int32)]
 
 
 class UNetConfigC(C.Structure):
@@ -125,6 +126,8 @@ SIGNATURES = {
     "pixie_conv_pack_weights": (_I, [_VP, _VP, _I, _I, _I, _VP]),
     "pixie_conv_packed16_bytes": (_I64, [_I, _I, _I]),
     "pixie_conv_pack_weights_f16x2": (_I, [_VP, _VP, _I, _I, _I, _VP]),
+    "pixie_conv_subpixel_bytes": (_I64, [_I, _I]),
+    "pixie_conv_pack_weights_subpixel": (_I, [_VP, _VP, _I, _I, _VP]),
     "pixie_conv3d_forward": (_I, [C.POINTER(ConvDesc), _VP]),
     "pixie_conv_stats_floats": (_I64, [C.POINTER(ConvDesc)]),
     "pixie_conv_workspace_bytes": (_I64, [C.POINTER(ConvDesc)]),

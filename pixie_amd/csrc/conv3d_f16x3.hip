@@ -103,8 +103,16 @@ __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned
 // [tap][c_in][c_out] weight array (L2-resident: 442 KB for the 64 -> 64 layer), fetched one tap ahead.
 // (Round 5 tried taking the dx = 1, 2 B fragments of a row from the neighbouring lane with v_mov_b32_dpp wave_shl:1 instead of two more
 // LDS reads: 1.45 vs 1.30 ms on the dominant layer, 1.97 vs 1.78 J per launch -- profiles/r5c_conv_dppb_rejected.txt.)
-template <int KS, int MB, int NB, bool EX = false>
+// SP ("sub-pixel"): a 3^3 convolution behind a nearest x2 upsampling, computed over the STORED tensor.  Output voxel 2i + p reads
+// floor((2i + p + d) / 2) for d = -1, 0, 1: i-1, i, i for p = 0 and i, i, i+1 for p = 1, so per axis two effective taps with
+// pre-summed weights (pack_weights_subpixel_kernel) and per output parity a 2x2x2 convolution: 8 taps instead of 27.  A
+// workgroup takes one (z, y) parity (tile index & 3) and BOTH x parities of a tile of 4 x 64 stored voxels: accumulator
+// block nb = 2 px + s holds x parity px of the wave's stored-voxel block s, so the transposing epilogue writes whole output
+// rows.  The tile is staged without the x2 replication with a halo of one voxel on the side the parity reads
+// (x: both sides), i.e. (TX + 2)(TY + 1)(TZ + 1) slots; A.ups is 0 and A.L* are the stored dims on this path.
+template <int KS, int MB, int NB, bool EX = false, bool SP = false>
 __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
+    static_assert(!SP || (KS == 3 && NB == 4 && !EX), "sub-pixel path: 3^3, two x parities x two voxel blocks per wave");
     extern __shared__ uint4 smem16[];
     constexpr int PAD = (KS == 3) ? 1 : 0;
     constexpr int NW = 4, NT = 64 * NW;     // (an 8-wave, one-workgroup-per-CU tile was measured in round 4: 1.350 vs 1.323 ms, profiles/r4k_conv_eight_wave_tile_rejected.txt)
@@ -125,12 +133,17 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         // exact only when n_tiles is a multiple of 8; otherwise keep the identity order
         if ((A.n_tiles & 7) == 0) t = cand;
     }
+    int par = 0;                                  // SP: (z, y) output parity of this workgroup
+    if constexpr (SP) { par = t & 3; t >>= 2; }
+    const int py = par & 1, pz = par >> 1;
     const int tx = t % A.tiles_x; t /= A.tiles_x;
     const int ty = t % A.tiles_y;
     const int tz = t / A.tiles_y;
-    const int ox0 = tx * A.TX, oy0 = ty * A.TY, oz0 = tz * A.TZ;
+    const int ox0 = tx * A.TX, oy0 = ty * A.TY, oz0 = tz * A.TZ;   // SP: in stored voxels
     const int cout0 = blockIdx.y * (MB * 32);
-    const int lx0 = ox0 * A.stride - PAD, ly0 = oy0 * A.stride - PAD, lz0 = oz0 * A.stride - PAD;
+    const int lx0 = SP ? ox0 - 1 : ox0 * A.stride - PAD;
+    const int ly0 = SP ? oy0 - 1 + py : oy0 * A.stride - PAD;
+    const int lz0 = SP ? oz0 - 1 + pz : oz0 * A.stride - PAD;
     const size_t ISP = (size_t)A.ID * A.IH * A.IW;
     const size_t OSP = (size_t)A.OD * A.OH * A.OW;
 
@@ -139,6 +152,20 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     bool valid[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
+        if constexpr (SP) {
+            const int px = nb >> 1;
+            const int j = (wave * 2 + (nb & 1)) * 32 + l31;
+            int x = j & (A.TX - 1);
+            int y = (j >> A.lTX) & (A.TY - 1);
+            int z = j >> (A.lTX + A.lTY);
+            const int gx = 2 * (ox0 + x) + px, gy = 2 * (oy0 + y) + py, gz = 2 * (oz0 + z) + pz;
+            const bool v = (z < A.TZ) && (gx < A.OW) && (gy < A.OH) && (gz < A.OD);
+            if (!v) { x = 0; y = 0; z = 0; }
+            voff[nb] = (z * A.HY + y) * A.HX + x + px + kh * A.CS;
+            ovox[nb] = v ? (gz * A.OH + gy) * A.OW + gx : 0;
+            valid[nb] = v;
+            continue;
+        }
         const int j = (wave * NB + nb) * 32 + l31;
         int x = j & (A.TX - 1);
         int y = (j >> A.lTX) & (A.TY - 1);
@@ -169,8 +196,8 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
 
     const int KG = A.cin >> 3;                              // 8-channel groups
     const size_t tap_stride = (size_t)KG * A.coutp;         // uint4 units
-    const size_t plane = (size_t)(KS * KS * KS) * tap_stride;
-    const uint4* wHi = A.w16 + kW16HeaderU4 + (size_t)kh * A.coutp + cout0 + l31;
+    const size_t plane = (size_t)(SP ? 64 : KS * KS * KS) * tap_stride;   // SP: [parity (pz, py, px)][tap (ez, ey, ex)]
+    const uint4* wHi = A.w16 + kW16HeaderU4 + (size_t)kh * A.coutp + cout0 + l31 + (size_t)(par * 16) * tap_stride;
     const uint4* wLo = wHi + plane;
     const float* wF = A.wf + (size_t)kh * A.coutp + cout0 + l31;     // EX: channel (2 kp + kh) of the pair, row l31 of block mb
 
@@ -320,6 +347,59 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         const uint4* ldsLo = buf + 2 * A.CS;
         const uint4* wh = wHi + (size_t)(c_base >> 3) * A.coutp;
         const uint4* wl = wLo + (size_t)(c_base >> 3) * A.coutp;
+        if constexpr (SP) {
+            // 16 steps of 2 MB MFMA triples: (ez, ey) rolled, (ex, px) unrolled; step (ez, ey, ex, px) multiplies the weights
+            // of x parity px, tap (ez, ey, ex) with the tile at halo offset (ez, ey, px + ex).  As below, the A fragments of
+            // the next step are fetched during this one.
+            f16x8 ah[MB], al[MB];
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) {
+                ah[mb] = __builtin_bit_cast(f16x8, wh[mb * 32]);
+                al[mb] = __builtin_bit_cast(f16x8, wl[mb * 32]);
+            }
+#pragma unroll 1
+            for (int zy = 0; zy < 4; ++zy) {
+                const int rowoff = ((zy >> 1) * A.HY + (zy & 1)) * A.HX;
+                const int zyn = zy < 3 ? zy + 1 : 3;              // last step: re-read a valid fragment (harmless)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int ex = q >> 1, px = q & 1;
+                    const size_t nxt = (q < 3) ? (size_t)(((q + 1) & 1) * 8 + zy * 2 + ((q + 1) >> 1)) * tap_stride : (size_t)(zyn * 2) * tap_stride;
+                    f16x8 ahn[MB], aln[MB];
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb) {
+                        ahn[mb] = __builtin_bit_cast(f16x8, wh[nxt + mb * 32]);
+                        aln[mb] = __builtin_bit_cast(f16x8, wl[nxt + mb * 32]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    f16x8 bh[2], bl[2];
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        bh[s] = __builtin_bit_cast(f16x8, ldsHi[voff[px * 2 + s] + rowoff + ex]);
+                        bl[s] = __builtin_bit_cast(f16x8, ldsLo[voff[px * 2 + s] + rowoff + ex]);
+                    }
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+                            acc[mb][px * 2 + s] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], bh[s], acc[mb][px * 2 + s], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+                            acc[mb][px * 2 + s] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bl[s], acc[mb][px * 2 + s], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+                            acc[mb][px * 2 + s] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bh[s], acc[mb][px * 2 + s], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb) { ah[mb] = ahn[mb]; al[mb] = aln[mb]; }
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);
+            return;
+        }
         f16x8 ah[MB], al[MB];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
@@ -383,7 +463,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             __syncthreads();
             mfma_chunk(c_base, smem16);
         }
-        if (!EX && A.sk_w16) {
+        if (!EX && !SP && A.sk_w16) {
             // ---- the block's 1x1x1 skip convolution, in the same accumulators (so that out = conv(h) + skip(x) leaves this
             // launch; the skip tensor is never written or re-read).  acc holds sum (w s_w)(x s_x); the skip products carry
             // (s_w' s_x') instead, so acc is first multiplied by (s_w' s_x') / (s_w s_x) -- a power of two, exact.
@@ -490,8 +570,10 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     float* red = reinterpret_cast<float*>(smem16);   // [4 waves][MB*32 rows][2], reused after the last chunk
     float wmax = 0.0f;
     // workgroup-uniform: every accumulator element of this tile is a real output
-    const bool full = A.epi_lds && cout0 + MB * 32 <= A.cout && (A.TX & 3) == 0 && (A.OW & 3) == 0 && NW * NB * 32 <= A.TX * A.TY * A.TZ &&
-                      ox0 + A.TX <= A.OW && oy0 + A.TY <= A.OH && oz0 + A.TZ <= A.OD;
+    const bool full = SP ? (A.epi_lds && cout0 + MB * 32 <= A.cout && (A.TX & 1) == 0 && (A.OW & 3) == 0 && NW * 64 <= A.TX * A.TY * A.TZ &&
+                            2 * (ox0 + A.TX) <= A.OW && 2 * (oy0 + A.TY) <= A.OH && 2 * (oz0 + A.TZ) <= A.OD)
+                         : (A.epi_lds && cout0 + MB * 32 <= A.cout && (A.TX & 3) == 0 && (A.OW & 3) == 0 && NW * NB * 32 <= A.TX * A.TY * A.TZ &&
+                            ox0 + A.TX <= A.OW && oy0 + A.TY <= A.OH && oz0 + A.TZ <= A.OD);
     if (full) {
         __syncthreads();   // every wave is done with the activation tile
         // Interior tile (every tile of the 128^3 layers).  The accumulators go through LDS (the activation tile is dead)
@@ -505,16 +587,19 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         constexpr int LPR = NB * 8;          // lanes per row (4 voxels each)
         constexpr int RPI = 32 / LPR;        // rows per half-wave per iteration
         const int rsub = l31 / LPR, colq = 4 * (l31 % LPR), nbq = colq >> 5;
-        const int jq = (wave * NB + nbq) * 32 + (colq & 31);
+        // SP: column 2 j + px of a wave's row is x parity px of its stored voxel j, so 4 columns are 4 x-consecutive outputs
+        const int jq = SP ? wave * 64 + (colq >> 1) : (wave * NB + nbq) * 32 + (colq & 31);
         const int xq = jq & (A.TX - 1), yq = (jq >> A.lTX) & (A.TY - 1), zq = jq >> (A.lTX + A.lTY);
-        const size_t ovq = ((size_t)(oz0 + zq) * A.OH + (oy0 + yq)) * A.OW + ox0 + xq;
+        const size_t ovq = SP ? ((size_t)(2 * (oz0 + zq) + pz) * A.OH + (2 * (oy0 + yq) + py)) * A.OW + 2 * (ox0 + xq)
+                              : ((size_t)(oz0 + zq) * A.OH + (oy0 + yq)) * A.OW + ox0 + xq;
         const bool has_res = A.residual != nullptr, has_stats = A.stats != nullptr;
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) ldsO[((r & 3) + 8 * (r >> 2) + 4 * kh) * LDO + nb * 32 + l31] = acc[mb][nb][r];
+                for (int nb = 0; nb < NB; ++nb)
+                    ldsO[((r & 3) + 8 * (r >> 2) + 4 * kh) * LDO + (SP ? 2 * ((nb & 1) * 32 + l31) + (nb >> 1) : nb * 32 + l31)] = acc[mb][nb][r];
 #pragma unroll 4
             for (int it = 0; it < 16 / RPI; ++it) {
                 const int rowl = (2 * it + kh) * RPI + rsub;
@@ -593,6 +678,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_f16x3_kernel(Conv16Args A) {
 template <int KS, int MB, int NB>
 __global__ __launch_bounds__(256, 2) void conv3d_exact_kernel(Conv16Args A) {
     conv3d_f16x3_body<KS, MB, NB, true>(A);
+}
+// Sub-pixel form of the 3^3 convolutions behind a nearest x2 upsampling (Upsample.conv): 8 taps per output instead of 27
+template <int MB>
+__global__ __launch_bounds__(256, 2) void conv3d_f16x3_subpixel_kernel(Conv16Args A) {
+    conv3d_f16x3_body<3, MB, 4, false, true>(A);
 }
 // The dominant layer of the BASELINE network -- 64 -> 64 channels, 3^3, stride 1, on >= 128^3 voxels (the full-resolution
 // level: 41 % of a scene's FLOPs at 128^3; the 64^3 level has the same channel counts and stays on the template) -- under its own symbol, so that `rocprofv3 --kernel-trace --stats` reports it as
@@ -673,9 +763,77 @@ __global__ void pack_weights_f16x2_kernel(const float* __restrict__ src, uint4* 
     dst[kW16HeaderU4 + total + i] = __builtin_bit_cast(uint4, vl);
 }
 
+// Sub-pixel weights of a 3^3 convolution behind a nearest x2 upsampling.  Per axis, output parity p and effective tap e
+// sum the original taps  p=0: e=0 {0}, e=1 {1,2};  p=1: e=0 {0,1}, e=1 {2}  (tap index 0..2 = offset -1..1), in fp32, in
+// ascending (dz, dy, dx) order.  par = (pz*2 + py)*2 + px, tap = (ez*2 + ey)*2 + ex.
+__device__ __forceinline__ float subpixel_weight(const float* __restrict__ w27, int par, int tap) {
+    int lo[3], hi[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {   // ax 0 = z
+        const int p = (par >> (2 - ax)) & 1, e = (tap >> (2 - ax)) & 1;
+        lo[ax] = e ? (p ? 2 : 1) : 0;
+        hi[ax] = e ? 2 : (p ? 1 : 0);
+    }
+    float sum = 0.0f;
+    for (int dz = lo[0]; dz <= hi[0]; ++dz)
+        for (int dy = lo[1]; dy <= hi[1]; ++dy)
+            for (int dx = lo[2]; dx <= hi[2]; ++dx) sum += w27[(dz * 3 + dy) * 3 + dx];
+    return sum;
+}
+// |w|max of the summed weights (float bits, atomicMax; caller zeroes the slot): one thread per (c_out, c_in) pair
+__global__ __launch_bounds__(256) void subpixel_amax_kernel(const float* __restrict__ src, long pairs, unsigned* __restrict__ slot) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    float m = 0.0f;
+    if (i < pairs)
+        for (int pt = 0; pt < 64; ++pt) m = fmaxf(m, fabsf(subpixel_weight(src + i * 27, pt >> 3, pt & 7)));
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
+    if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(slot, __float_as_uint(m));
+}
+// (c_out, c_in, 27) fp32 -> header + hi planes + lo planes of [parity 8][tap 8][c_in/8][c_out_padded] x (8 x fp16); the
+// split is pack_weights_f16x2_kernel's, applied to the summed weights
+__global__ void pack_weights_subpixel_kernel(const float* __restrict__ src, uint4* __restrict__ dst, int cout, int cin, int coutp,
+                                             const unsigned* __restrict__ amax_bits) {
+    const int KG = cin >> 3;
+    const long total = 64L * KG * coutp;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int e = scale_exponent(__uint_as_float(*amax_bits));
+    if (i == 0) dst[0] = make_uint4(__float_as_uint(pow2i(-e)), (unsigned)cout, (unsigned)cin, 64u);
+    if (i >= total) return;
+    const float s = pow2i(e);
+    const int co = (int)(i % coutp);
+    const long row = i / coutp;
+    const int kg = (int)(row % KG);
+    const int pt = (int)(row / KG);
+    f16x8 vh, vl;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float w = 0.0f;
+        if (co < cout) w = subpixel_weight(src + ((long)co * cin + kg * 8 + j) * 27, pt >> 3, pt & 7) * s;
+        const _Float16 h = (_Float16)w;
+        vh[j] = h;
+        vl[j] = (_Float16)(w - (float)h);
+    }
+    dst[kW16HeaderU4 + i] = __builtin_bit_cast(uint4, vh);
+    dst[kW16HeaderU4 + total + i] = __builtin_bit_cast(uint4, vl);
+}
+
 static unsigned magic_of16(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
 static int ilog2_16(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static int pow2_le16(int v, int cap) { int p = 1; while (p * 2 <= v && p * 2 <= cap) p *= 2; return p; }
+
+template <int MB>
+static int launch_subpixel(const Conv16Args& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
+    auto kern = conv3d_f16x3_subpixel_kernel<MB>;
+    PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// does this descriptor take the sub-pixel path (w16_subpixel says how d_w16 was packed; the shape must allow it)
+static bool conv16_subpixel(const pixie_conv_desc* d) {
+    return d->d_w16 && d->w16_subpixel && d->upsample == 1 && d->ksize == 3 && d->stride == 1;
+}
 
 template <int KS, int MB, int NB>
 static int launch_f16x3(const Conv16Args& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
@@ -698,6 +856,31 @@ static void conv16_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, 
     if (d->out_h > 0) a.OH = std::min(a.OH, (int)d->out_h);
     if (d->out_w > 0) a.OW = std::min(a.OW, (int)d->out_w);
     a.cout = d->c_out; a.coutp = pixie_conv_cout_padded(d->c_out);
+    const int chunks = (d->c0 + d->c1) / 16;
+    const int smax = d->d_workspace ? std::min(8, chunks / 2) : 1;
+    if (conv16_subpixel(d)) {
+        // the tile lies over the STORED voxels that have an output: 4 waves x 64 voxels, each worth two x parities; one
+        // workgroup per tile and (z, y) parity, the parity fastest: where the body's XCD remap applies and the tile count is a
+        // multiple of 8 (every shape of the 128^3 network) the four parities of a tile run in one XCD and share their input in
+        // its L2; otherwise they may straddle XCDs and meet in the MALL instead (performance only)
+        a.ups = 0; a.LD = a.ID; a.LH = a.IH; a.LW = a.IW;
+        const int SD = (a.OD + 1) / 2, SH = (a.OH + 1) / 2, SW = (a.OW + 1) / 2;
+        a.TX = pow2_le16(SW, 32);
+        a.TY = pow2_le16(SH, std::max(1, std::min(4, 256 / a.TX)));
+        a.TZ = std::max(1, std::min(SD, 256 / (a.TX * a.TY)));
+        a.lTX = ilog2_16(a.TX); a.lTY = ilog2_16(a.TY);
+        a.tiles_x = (SW + a.TX - 1) / a.TX; a.tiles_y = (SH + a.TY - 1) / a.TY; a.tiles_z = (SD + a.TZ - 1) / a.TZ;
+        a.n_tiles = 4 * a.tiles_x * a.tiles_y * a.tiles_z;
+        a.HX = a.TX + 2; a.HY = a.TY + 1; a.HZ = a.TZ + 1;
+        a.HYX = a.HY * a.HX; a.CS = a.HZ * a.HYX;
+        a.mHX = magic_of16(a.HX); a.mHYX = magic_of16(a.HYX);
+        MB_out = (a.coutp >= 64) ? 2 : 1; NB_out = 4;
+        int sl = 1;   // too few workgroups for the chip: split the channel chunks (needs the caller's workspace)
+        const long wgs = (long)a.n_tiles * ((a.coutp + MB_out * 32 - 1) / (MB_out * 32));
+        while (sl * 2 <= smax && wgs * sl < 512) sl *= 2;
+        if (slices_out) *slices_out = sl;
+        return;
+    }
     const long ovol = (long)a.OD * a.OH * a.OW;
     int MB = (a.coutp >= 64) ? 2 : 1;
     int NB = (a.stride == 2) ? 1 : 4;   // stride 2: the tile holds 8x the voxels it produces; only NB = 1 fits (112 KB, one workgroup per CU)
@@ -709,8 +892,6 @@ static void conv16_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, 
     // big MFMA-efficient tile and split the channel chunks over up to 8 slices instead of shrinking the tile; the
     // slices write partial outputs that splitk_reduce_kernel adds in a fixed order.
     int slices = 1;
-    const int chunks = (d->c0 + d->c1) / 16;
-    const int smax = d->d_workspace ? std::min(8, chunks / 2) : 1;
     if (smax >= 2 && n_wg(MB, NB) < 512) {
         bool found = false;
         for (int nb = NB; nb >= 1 && !found; nb /= 2) {
@@ -762,7 +943,9 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
     a.stats = d->d_out_stats; a.out_amax = d->d_out_amax;
 
     int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(d, a, MB, NB, &slices);
+    const bool sp = d->w16_subpixel != 0;
+    PX_REQUIRE(!sp || (conv16_subpixel(d) && !d->d_skip_w16), "f16x3 conv: sub-pixel weights need upsample = 1, ksize = 3, stride = 1 and no folded skip");
+    conv16_tiling(d, a, MB, NB, &slices);   // (sub-pixel: a.ups, a.L* now describe the stored tensor)
     if (d->d_skip_w16) {
         const int scin = d->skip_c0 + d->skip_c1;
         PX_REQUIRE(pixie_conv_skip_foldable(d), "f16x3 conv: this launch cannot fold a skip convolution (pixie_conv_skip_foldable)");
@@ -786,11 +969,15 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)), (unsigned)slices);
     if (slices > 1) {
         int rc = 1;
+        if (sp) {
+            rc = (MB == 2) ? launch_subpixel<2>(a, lds, grid, st) : launch_subpixel<1>(a, lds, grid, st);
+        } else {
 #define PX_CONV16_SK(KS_, MB_, NB_) \
-        if (d->ksize == KS_ && MB == MB_ && NB == NB_) rc = launch_f16x3<KS_, MB_, NB_>(a, lds, grid, st);
-        PX_CONV16_SK(3, 2, 4) PX_CONV16_SK(3, 2, 2) PX_CONV16_SK(3, 2, 1) PX_CONV16_SK(3, 1, 4) PX_CONV16_SK(3, 1, 2) PX_CONV16_SK(3, 1, 1)
-        PX_CONV16_SK(1, 2, 4) PX_CONV16_SK(1, 2, 2) PX_CONV16_SK(1, 2, 1) PX_CONV16_SK(1, 1, 4) PX_CONV16_SK(1, 1, 2) PX_CONV16_SK(1, 1, 1)
+            if (d->ksize == KS_ && MB == MB_ && NB == NB_) rc = launch_f16x3<KS_, MB_, NB_>(a, lds, grid, st);
+            PX_CONV16_SK(3, 2, 4) PX_CONV16_SK(3, 2, 2) PX_CONV16_SK(3, 2, 1) PX_CONV16_SK(3, 1, 4) PX_CONV16_SK(3, 1, 2) PX_CONV16_SK(3, 1, 1)
+            PX_CONV16_SK(1, 2, 4) PX_CONV16_SK(1, 2, 2) PX_CONV16_SK(1, 2, 1) PX_CONV16_SK(1, 1, 4) PX_CONV16_SK(1, 1, 2) PX_CONV16_SK(1, 1, 1)
 #undef PX_CONV16_SK
+        }
         if (rc) return rc;
         const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, slices, n_elems, osp,
@@ -798,6 +985,7 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
         PX_CHECK_HIP(hipGetLastError());
         return 0;
     }
+    if (sp) return (MB == 2) ? launch_subpixel<2>(a, lds, grid, st) : launch_subpixel<1>(a, lds, grid, st);
     if (d->ksize == 3 && MB == 2 && NB == 4 && cin == 64 && d->c_out == 64 && d->stride == 1 && !d->upsample && d->c1 == 0 && !a.sk_w16 &&
         (long)a.OD * a.OH * a.OW >= 128L * 128 * 128) {
         auto kern = conv3d_f16x3_c64_fullres_kernel;
@@ -896,6 +1084,7 @@ extern "C" int pixie_conv_kernel_variant(const pixie_conv_desc* d, int* slices_o
     int MB = 0, NB = 0, slices = 1;
     conv16_tiling(d, a, MB, NB, &slices);
     if (slices_out) *slices_out = slices;
+    if (conv16_subpixel(d)) return 8300 + MB * 10 + NB;   // conv3d_f16x3_subpixel_kernel<MB>
     if (d->ksize == 3 && MB == 2 && NB == 4 && d->c0 + d->c1 == 64 && d->c_out == 64 && d->stride == 1 && !d->upsample && d->c1 == 0 && !d->d_skip_w16 &&
         (long)a.OD * a.OH * a.OW >= 128L * 128 * 128)
         return 9324;   // conv3d_f16x3_c64_fullres_kernel: the <3,2,4> code under its own symbol
@@ -951,6 +1140,29 @@ extern "C" int pixie_conv_pack_weights_f16x2(const float* d_w, void* d_packed, i
     const long total = (long)taps * (c_in / 8) * coutp;
     hipLaunchKernelGGL(pack_weights_f16x2_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, d_w, reinterpret_cast<uint4*>(d_packed), c_out,
                        c_in, taps, coutp, slot);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t pixie_conv_subpixel_bytes(int c_out, int c_in) {
+    if (c_out <= 0 || c_in <= 0 || c_in % 16 != 0) return 0;
+    return ((int64_t)kW16HeaderU4 + 2 * 64 * (int64_t)(c_in / 8) * pixie_conv_cout_padded(c_out)) * (int64_t)sizeof(uint4);
+}
+
+extern "C" int pixie_conv_pack_weights_subpixel(const float* d_w, void* d_packed, int c_out, int c_in, void* stream) {
+    PX_REQUIRE(d_w && d_packed && c_out > 0 && c_in > 0 && c_in % 16 == 0,
+               "pixie_conv_pack_weights_subpixel: bad arguments (c_in must be a multiple of 16)");
+    hipStream_t st = as_stream(stream);
+    const int coutp = pixie_conv_cout_padded(c_out);
+    // as in pixie_conv_pack_weights_f16x2: the |w|max slot lives in the header's last word until the header is written
+    unsigned* slot = reinterpret_cast<unsigned*>(d_packed) + 15;
+    PX_CHECK_HIP(hipMemsetAsync(d_packed, 0, kW16HeaderU4 * sizeof(uint4), st));
+    const long pairs = (long)c_out * c_in;
+    hipLaunchKernelGGL(subpixel_amax_kernel, dim3(cdiv(pairs, 256)), dim3(256), 0, st, d_w, pairs, slot);
+    PX_CHECK_HIP(hipGetLastError());
+    const long total = 64L * (c_in / 8) * coutp;
+    hipLaunchKernelGGL(pack_weights_subpixel_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, d_w, reinterpret_cast<uint4*>(d_packed), c_out,
+                       c_in, coutp, slot);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -254,7 +254,9 @@ extern "C" int pixie_conv3d_forward(const pixie_conv_desc* d, void* stream) {
     PX_REQUIRE(d->c_out > 0 && d->in_d > 0 && d->in_h > 0 && d->in_w > 0, "pixie_conv3d_forward: bad sizes");
     PX_REQUIRE((d->d_pro_a == nullptr) == (d->d_pro_b == nullptr), "pixie_conv3d_forward: pro_a/pro_b must come together");
     PX_REQUIRE((d->d_gamma == nullptr) == (d->d_beta == nullptr), "pixie_conv3d_forward: gamma/beta must come together");
-    PX_REQUIRE(!(d->d_gamma && d->upsample), "pixie_conv3d_forward: spatial affine with upsample is not in the reference graph");
+    // (the sub-pixel path runs over the stored tensor, so its prologue takes gamma/beta of the STORED grid like any other layer)
+    PX_REQUIRE(!(d->d_gamma && d->upsample) || (d->d_w16 && d->w16_subpixel),
+               "pixie_conv3d_forward: spatial affine with upsample needs the sub-pixel path (w16_subpixel), with gamma/beta of the stored grid");
 
     if (d->d_w16) return conv3d_f16x3_forward(d, as_stream(stream));
     PX_REQUIRE(!d->d_skip_w16, "pixie_conv3d_forward: a folded skip convolution needs the f16x3 path (d_w16)");

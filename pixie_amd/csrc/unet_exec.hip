@@ -259,7 +259,7 @@ struct pixie_unet {
     uint32_t* d_bound_slots = nullptr;     // 2 words per normalisation layer, device
     std::vector<uint32_t> h_bound_slots;
     std::map<std::tuple<int, int, int, bool>, Sized> sized;   // (d, h, w, starts behind projector.net[0]) -> what one pass needs
-    bool fuse_stats = true, split_k = true, fold_skip = true;
+    bool fuse_stats = true, split_k = true, fold_skip = true, subpixel = true;
     // pixie_unet_set_option("graph", 1): forward() replays a captured HIP graph when called again with the same pointers
     struct Replay { const float* feat; const float* proj0; float* out; void* ws; int d; uint64_t epoch; hipGraph_t graph; hipGraphExec_t exec; };
     bool use_graph = false;
@@ -322,17 +322,18 @@ struct Exec {
         if (!dry && !p.d) fail("pixie_unet_forward: parameter '%s' was never set", key.c_str());
         return p.d;
     }
-    const void* w16(const std::string& key) {     // f16 hi/lo packing, once per parameter version
+    const void* w16(const std::string& key, bool subpixel = false) {     // f16 hi/lo packing (or its sub-pixel form), once per parameter version
         const Param& p = net->param(key + ".weight");
         if (dry) return nullptr;
-        Packed& e = net->packed16[key];
+        Packed& e = net->packed16[subpixel ? key + "#subpixel" : key];
         if (e.version != p.version) {
             const int cout = (int)p.shape[0], cin = (int)p.shape[1], k = (int)p.shape[2];
-            const int64_t nb = pixie_conv_packed16_bytes(cout, cin, k);
+            const int64_t nb = subpixel ? (k == 3 ? pixie_conv_subpixel_bytes(cout, cin) : 0) : pixie_conv_packed16_bytes(cout, cin, k);
             if (nb <= 0) fail("pixie_unet: '%s' cannot take the f16x3 packing (c_in %d)", key.c_str(), cin);
             if (!e.d && hipMalloc(&e.d, (size_t)nb) != hipSuccess) fail("pixie_unet: hipMalloc of %lld bytes failed", (long long)nb);
             if (!p.d) fail("pixie_unet_forward: parameter '%s.weight' was never set", key.c_str());
-            ok(pixie_conv_pack_weights_f16x2(p.d, e.d, cout, cin, k, stream), "pixie_conv_pack_weights_f16x2");
+            if (subpixel) ok(pixie_conv_pack_weights_subpixel(p.d, e.d, cout, cin, stream), "pixie_conv_pack_weights_subpixel");
+            else ok(pixie_conv_pack_weights_f16x2(p.d, e.d, cout, cin, k, stream), "pixie_conv_pack_weights_f16x2");
             e.version = p.version;
         }
         return e.d;
@@ -443,7 +444,9 @@ struct Exec {
             if (!dry) ok(pixie_conv3d_forward(&desc, stream), "pixie_conv3d_forward");
             return out;
         }
-        desc.d_w16 = w16(wkey);
+        const bool sub = net->subpixel && o.upsample && ksize == 3 && o.stride == 1;   // unet.py: UNetRunner._conv
+        desc.d_w16 = w16(wkey, sub);
+        desc.w16_subpixel = sub ? 1 : 0;
         if (o.skip_parts) {
             const std::vector<TP>& sp = *o.skip_parts;
             desc.d_skip_in0 = sp[0]->p; desc.skip_c0 = sp[0]->c;
@@ -721,6 +724,7 @@ extern "C" int pixie_unet_create(pixie_unet** out, const pixie_unet_config* c) {
         const char* fs = getenv("PIXIE_FUSE_STATS"); n->fuse_stats = !(fs && fs[0] == '0');
         const char* sk = getenv("PIXIE_CONV_SPLIT_K"); n->split_k = !(sk && sk[0] == '0');
         const char* fk = getenv("PIXIE_FOLD_SKIP"); n->fold_skip = !(fk && fk[0] == '0');
+        const char* sx = getenv("PIXIE_CONV_SUBPIXEL"); n->subpixel = !(sx && sx[0] == '0');
         *out = n.release();
         return 0;
     });

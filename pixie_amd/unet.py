@@ -84,6 +84,18 @@ class HipOps:
         check(self.lib.pixie_conv_pack_weights_f16x2(_ptr(w), _ptr(packed), cout, cin, k, self.stream), "pixie_conv_pack_weights_f16x2")
         return packed
 
+    def pack_conv_subpixel(self, weight: torch.Tensor) -> torch.Tensor:
+        """Sub-pixel f16x3 packing of the 3^3 weight of a convolution behind a nearest x2 upsampling (conv(..., subpixel=True)):
+        per output parity the taps that read the same stored voxel are summed, 8 parities x 8 taps."""
+        cout, cin = weight.shape[0], weight.shape[1]
+        nbytes = self.lib.pixie_conv_subpixel_bytes(cout, cin) if tuple(weight.shape[2:]) == (3, 3, 3) else 0
+        if nbytes <= 0:
+            raise _lib.PixieHipError(f"sub-pixel packing needs a 3x3x3 weight with c_in % 16 == 0 (got {tuple(weight.shape)})")
+        w = weight.detach().to(self.device, torch.float32).contiguous()
+        packed = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        check(self.lib.pixie_conv_pack_weights_subpixel(_ptr(w), _ptr(packed), cout, cin, self.stream), "pixie_conv_pack_weights_subpixel")
+        return packed
+
     @staticmethod
     def f16x3_ok(parts: Sequence[torch.Tensor], stride: int) -> bool:
         cin = sum(int(p.shape[0]) for p in parts)
@@ -95,8 +107,8 @@ class HipOps:
              residual: Optional[torch.Tensor] = None, w16: Optional[torch.Tensor] = None,
              in_amax: Optional[Sequence[torch.Tensor]] = None, in_bound: float = 0.0,
              out_amax: Optional[torch.Tensor] = None, out_size: Optional[Tuple[int, int, int]] = None,
-             skip: Optional[dict] = None):
-        """Returns the output tensor; with `out_amax` (f16x3 path) returns (output, channel sums float64 (c_out, 2))
+             skip: Optional[dict] = None, subpixel: bool = False):
+        """`subpixel`: w16 comes from pack_conv_subpixel (upsample, 3^3, stride 1 only).  Returns the output tensor; with `out_amax` (f16x3 path) returns (output, channel sums float64 (c_out, 2))
         computed in the conv epilogue, and atomicMax'es |output|max into out_amax."""
         x0 = parts[0]
         x1 = parts[1] if len(parts) > 1 else None
@@ -125,6 +137,7 @@ class HipOps:
         desc.act = act
         desc.d_w = packed_w.data_ptr() if packed_w is not None else None
         desc.d_w16 = w16.data_ptr() if w16 is not None else None
+        desc.w16_subpixel = 1 if subpixel else 0
         desc.d_in_amax0 = in_amax[0].data_ptr() if in_amax else None
         desc.d_in_amax1 = in_amax[1].data_ptr() if in_amax and len(in_amax) > 1 else None
         desc.in_bound = float(in_bound)
@@ -246,6 +259,7 @@ class UNetRunner:
         self._bounds: Dict[str, Tuple[int, int, float, float]] = {}
         self.fuse_stats = os.environ.get("PIXIE_FUSE_STATS", "1") != "0"   # channel statistics in the conv epilogue
         self.fold_skip = os.environ.get("PIXIE_FOLD_SKIP", "1") != "0"     # skip_connection 1x1x1 inside the block's second conv
+        self.subpixel = os.environ.get("PIXIE_CONV_SUBPIXEL", "1") != "0"  # up-convs as 8 parities x 2^3 taps over the stored tensor
 
     @property
     def _f16x3(self) -> bool:
@@ -259,12 +273,13 @@ class UNetRunner:
             self._packed[key] = (t.data_ptr(), t._version, self.ops.pack_conv(t))
         return self._packed[key][2]
 
-    def _w16(self, key: str) -> torch.Tensor:
+    def _w16(self, key: str, subpixel: bool = False) -> torch.Tensor:
         t = self.p[key + ".weight"]
-        ent = self._packed16.get(key)
+        ck = key + "#subpixel" if subpixel else key
+        ent = self._packed16.get(ck)
         if ent is None or ent[0] != t.data_ptr() or ent[1] != t._version:
-            self._packed16[key] = (t.data_ptr(), t._version, self.ops.pack_conv16(t))
-        return self._packed16[key][2]
+            self._packed16[ck] = (t.data_ptr(), t._version, self.ops.pack_conv_subpixel(t) if subpixel else self.ops.pack_conv16(t))
+        return self._packed16[ck][2]
 
     def _b(self, key: str) -> torch.Tensor:
         return self.p[key + ".bias"]
@@ -340,16 +355,20 @@ class UNetRunner:
             kw["out_size"] = out_size
         if skip is not None:
             kw["skip"] = skip
+        # (unet_exec.hip: Exec::conv takes the same decision; injected reference operators keep the 27-tap form)
+        sub = self.subpixel and upsample and ksize == 3 and stride == 1 and hasattr(ops, "pack_conv_subpixel")
+        if sub:
+            kw["subpixel"] = True
         if self.fuse_stats:
             # the output's channel sums and |x|max come out of the conv epilogue: no separate pass over the tensor
             slot = self._new_slot(cache, parts[0].device)
             out, sums = ops.conv(parts, None, self._b(wkey), cout, ksize, stride=stride, upsample=upsample, pro=pro, affine=affine,
-                                 act=act, residual=residual, w16=self._w16(wkey), out_amax=slot, **kw)
+                                 act=act, residual=residual, w16=self._w16(wkey, sub), out_amax=slot, **kw)
             if sums is not None:
                 self._remember(cache, out, sums, slot)
             return out
         return ops.conv(parts, None, self._b(wkey), cout, ksize, stride=stride, upsample=upsample, pro=pro, affine=affine,
-                        act=act, residual=residual, w16=self._w16(wkey), **kw)
+                        act=act, residual=residual, w16=self._w16(wkey, sub), **kw)
 
     # -- blocks
     def _res(self, b: Block, parts: List[torch.Tensor], cache: dict) -> torch.Tensor:

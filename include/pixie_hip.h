@@ -499,6 +499,14 @@ int pixie_mpm_kernel_times(pixie_mpm* h, double* particle_ms, double* grid_ms, i
  * code under its own symbol for the 64 -> 64 full-resolution 3^3 layers), 0 = the exact-fp32 kernel.  For profilers that
  * want to group per-launch timings by kernel name, as rocprofv3 does; no reference counterpart. */
 int pixie_conv_kernel_variant(const pixie_conv_desc* desc, int* slices);
+
+/* The tiling pixie_conv3d_forward launches this descriptor with, from the launchers' own selection code (a pure host function of
+ * the descriptor; no device needed): out = TX, TY, TZ (tile extents in output voxels; sub-pixel launches: in STORED voxels, each
+ * tile being four (z, y)-parity workgroups), tiles_x, tiles_y, tiles_z, epi_lds (1 = the launch reserves LDS for the transposing
+ * epilogue), slices (split-K factor), MB, NB.  With desc->d_w16 set it describes the f16x3 launch, otherwise the exact-fp32
+ * launch of the same tiled body.  Returns 1 for descriptors that take neither (the first-generation exact kernel).  For tests that
+ * must know which kernel variant and tile geometry a shape exercises. */
+int pixie_conv_tile_geometry(const pixie_conv_desc* desc, int32_t out[10]);
 #endif /* PIXIE_DIAG */
 
 #ifdef __cplusplus

@@ -168,6 +168,7 @@ DIAG_SIGNATURES = {
     "pixie_mpm_phase": (_I, [_VP, _I, _D, _VP]),
     "pixie_mpm_kernel_times": (_I, [_VP, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     "pixie_conv_kernel_variant": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),
+    "pixie_conv_tile_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
 }
 
 _libs = {}

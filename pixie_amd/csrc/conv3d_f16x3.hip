@@ -918,6 +918,21 @@ static void conv16_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, 
     MB_out = MB; NB_out = NB;
 }
 
+// LDS the transposing epilogue needs (4 waves x 32 rows x (NB*32 + 4) floats + the statistics partials), and whether a launch
+// gets it: unsplit launches only, as long as two workgroups still fit on a CU.  One decision for both launchers and for
+// pixie_conv_tile_geometry.
+static size_t conv16_epi_bytes(int MB, int NB) { return ((size_t)4 * 32 * (NB * 32 + 4) + (size_t)4 * MB * 32 * 2) * sizeof(float); }
+static bool conv16_epi_lds(int MB, int NB, int slices) { return slices == 1 && conv16_epi_bytes(MB, NB) <= 80 * 1024; }
+
+// the exact-fp32 launch's tiling: conv16_tiling without a workspace (no split-K on this path: small layers shrink the tile instead)
+static void conv16_exact_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, int& NB_out) {
+    pixie_conv_desc probe = *d;
+    probe.d_workspace = nullptr;
+    probe.w16_subpixel = 0;
+    int slices = 1;
+    conv16_tiling(&probe, a, MB_out, NB_out, &slices);
+}
+
 // called by pixie_conv3d_forward (conv3d_mfma.hip) when the descriptor carries f16x2-packed weights
 int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
     PX_REQUIRE(d->stride == 1 || (d->stride == 2 && d->ksize == 3 && !d->upsample), "f16x3 conv: stride must be 1, or 2 for a 3^3 kernel");
@@ -962,10 +977,7 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
 
     size_t lds = (size_t)4 * a.CS * sizeof(uint4);
     PX_REQUIRE(lds <= 160 * 1024, "f16x3 conv: tile needs %zu B of LDS", lds);
-    {   // room for the transposing epilogue, as long as two workgroups still fit on a CU
-        const size_t epi = ((size_t)4 * 32 * (NB * 32 + 4) + (size_t)4 * MB * 32 * 2) * sizeof(float);
-        if (slices == 1 && epi <= 80 * 1024) { a.epi_lds = 1; if (lds < epi) lds = epi; }
-    }
+    if (conv16_epi_lds(MB, NB, slices)) { a.epi_lds = 1; lds = std::max(lds, conv16_epi_bytes(MB, NB)); }   // room for the transposing epilogue
     const dim3 grid((unsigned)a.n_tiles, (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)), (unsigned)slices);
     if (slices > 1) {
         int rc = 1;
@@ -1028,16 +1040,11 @@ int conv3d_exact_forward(const pixie_conv_desc* d, hipStream_t st) {
     a.wf = d->d_w; a.bias = d->d_bias;
     a.residual = d->d_residual; a.out = d->d_out;
     a.in_bound = 1.0f;
-    pixie_conv_desc probe = *d;
-    probe.d_workspace = nullptr;            // no split-K on this path: small layers shrink the tile instead
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(&probe, a, MB, NB, &slices);
+    int MB = 0, NB = 0;
+    conv16_exact_tiling(d, a, MB, NB);
     size_t lds = (size_t)4 * a.CS * sizeof(uint4);      // 16 fp32 planes = the four 16-byte fp16 planes
     PX_REQUIRE(lds <= 160 * 1024, "exact conv: tile needs %zu B of LDS", lds);
-    {   // room for the transposing epilogue, as long as two workgroups still fit on a CU
-        const size_t epi = ((size_t)4 * 32 * (NB * 32 + 4) + (size_t)4 * MB * 32 * 2) * sizeof(float);
-        if (epi <= 80 * 1024) { a.epi_lds = 1; if (lds < epi) lds = epi; }
-    }
+    if (conv16_epi_lds(MB, NB, 1)) { a.epi_lds = 1; lds = std::max(lds, conv16_epi_bytes(MB, NB)); }   // room for the transposing epilogue
     const dim3 grid((unsigned)a.n_tiles, (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)), 1u);
 #define PX_CONVEX_CASE(KS_, MB_, NB_) \
     if (d->ksize == KS_ && MB == MB_ && NB == NB_) return launch_exact<KS_, MB_, NB_>(a, lds, grid, st);
@@ -1089,6 +1096,22 @@ extern "C" int pixie_conv_kernel_variant(const pixie_conv_desc* d, int* slices_o
         (long)a.OD * a.OH * a.OW >= 128L * 128 * 128)
         return 9324;   // conv3d_f16x3_c64_fullres_kernel: the <3,2,4> code under its own symbol
     return d->ksize * 100 + MB * 10 + NB;
+}
+
+// the tiling pixie_conv3d_forward launches this descriptor with: out = TX, TY, TZ, tiles_x, tiles_y, tiles_z, epi_lds, slices,
+// MB, NB.  With d_w16 the f16x3 launch (sub-pixel: the tile lies over the STORED voxels, each tile is four workgroups);
+// without, the exact-fp32 launch of the same body.  Returns 1 (and leaves out alone) for descriptors that take neither.
+extern "C" int pixie_conv_tile_geometry(const pixie_conv_desc* d, int32_t out[10]) {
+    if (!d || !out || (d->ksize != 1 && d->ksize != 3) || !(d->stride == 1 || (d->stride == 2 && d->ksize == 3 && !d->upsample))) return 1;
+    if ((d->c0 + d->c1) % 16 != 0 || (d->d_w16 && d->c0 % 8 != 0)) return 1;
+    if (!d->d_w16 && !conv3d_exact_tiled_ok(d)) return 1;
+    Conv16Args a{};
+    int MB = 0, NB = 0, slices = 1;
+    if (d->d_w16) conv16_tiling(d, a, MB, NB, &slices);
+    else conv16_exact_tiling(d, a, MB, NB);
+    const int32_t v[10] = {a.TX, a.TY, a.TZ, a.tiles_x, a.tiles_y, a.tiles_z, conv16_epi_lds(MB, NB, slices) ? 1 : 0, slices, MB, NB};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 0;
 }
 #endif
 

@@ -44,6 +44,78 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _addr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def fill_conv_desc(lib, alloc, parts: Sequence[torch.Tensor], packed_w, bias, cout: int, ksize: int, *, stride: int = 1,
+                   upsample: bool = False, pro=None, affine=None, act: int = 0, residual=None, w16=None, in_amax=None,
+                   in_bound: float = 0.0, out_amax=None, out_size=None, skip=None, subpixel: bool = False, split_k: bool = True,
+                   addr=_addr):
+    """The pixie_conv_desc of one convolution launch, as HipOps.conv issues it: geometry, operands, the split-K workspace where
+    the library says the layer splits (f16x3 path, `split_k`) and the epilogue-statistics buffer where `out_amax` asks for one
+    and the layer has one.  `alloc(shape, dtype)` makes the output / workspace / statistics tensors, `addr(tensor)` is their
+    address: the product passes device tensors; a test that only wants to know WHAT would be launched passes shape-only
+    tensors and a non-null stand-in address (no field is dereferenced here).  Returns (desc, out, stats, workspace)."""
+    x0 = parts[0]
+    x1 = parts[1] if len(parts) > 1 else None
+    cin0, d, h, w = x0.shape
+    up = 2 if upsample else 1
+    pad = 1 if ksize == 3 else 0
+    od = (d * up + 2 * pad - ksize) // stride + 1
+    oh = (h * up + 2 * pad - ksize) // stride + 1
+    ow = (w * up + 2 * pad - ksize) // stride + 1
+    desc = ConvDesc()
+    if out_size is not None:   # odd-grid crop (diffusion_network.py:925-930): the cropped voxels are never computed
+        od, oh, ow = min(od, int(out_size[0])), min(oh, int(out_size[1])), min(ow, int(out_size[2]))
+        desc.out_d, desc.out_h, desc.out_w = od, oh, ow
+    out = alloc((cout, od, oh, ow), torch.float32)
+    desc.d_in0 = addr(x0); desc.c0 = cin0
+    desc.d_in1 = addr(x1)
+    desc.c1 = x1.shape[0] if x1 is not None else 0
+    desc.in_d, desc.in_h, desc.in_w = d, h, w
+    desc.upsample = 1 if upsample else 0
+    desc.stride = stride
+    desc.ksize = ksize
+    desc.d_pro_a = addr(pro[0]) if pro is not None else None
+    desc.d_pro_b = addr(pro[1]) if pro is not None else None
+    desc.d_gamma = addr(affine[0]) if affine is not None else None
+    desc.d_beta = addr(affine[1]) if affine is not None else None
+    desc.act = act
+    desc.d_w = addr(packed_w)
+    desc.d_w16 = addr(w16)
+    desc.w16_subpixel = 1 if subpixel else 0
+    desc.d_in_amax0 = addr(in_amax[0]) if in_amax else None
+    desc.d_in_amax1 = addr(in_amax[1]) if in_amax and len(in_amax) > 1 else None
+    desc.in_bound = float(in_bound)
+    desc.d_bias = addr(bias)
+    desc.c_out = cout
+    desc.d_residual = addr(residual)
+    desc.d_out = addr(out)
+    if skip is not None:   # folded 1x1x1 skip convolution: dict(parts, w16, bias, amax)
+        sp = skip["parts"]
+        desc.d_skip_in0 = addr(sp[0]); desc.skip_c0 = sp[0].shape[0]
+        desc.d_skip_in1 = addr(sp[1]) if len(sp) > 1 else None
+        desc.skip_c1 = sp[1].shape[0] if len(sp) > 1 else 0
+        desc.d_skip_w16 = addr(skip["w16"])
+        desc.d_skip_bias = addr(skip["bias"])
+        desc.d_skip_amax0 = addr(skip["amax"][0])
+        desc.d_skip_amax1 = addr(skip["amax"][1]) if len(sp) > 1 else None
+    stats = workspace = None
+    if w16 is not None and split_k:
+        wsb = lib.pixie_conv_workspace_bytes(C.byref(desc))
+        if wsb > 0:   # small-output layer: split-K scratch (torch's caching allocator makes this a pointer bump)
+            workspace = alloc((wsb,), torch.uint8)
+            desc.d_workspace = addr(workspace)
+    if out_amax is not None and w16 is not None:
+        nfl = lib.pixie_conv_stats_floats(C.byref(desc))
+        if nfl > 0:
+            stats = alloc((nfl,), torch.float32)
+            desc.d_out_stats = addr(stats)
+            desc.d_out_amax = addr(out_amax)
+    return desc, out, stats, workspace
+
+
 class HipOps:
     """Operator set backed by include/pixie_hip.h (section A).  All tensors are fp32 CUDA(HIP) tensors
     without batch dimension: activations (C, D, H, W), attention (C, T)."""
@@ -110,62 +182,11 @@ class HipOps:
              skip: Optional[dict] = None, subpixel: bool = False):
         """`subpixel`: w16 comes from pack_conv_subpixel (upsample, 3^3, stride 1 only).  Returns the output tensor; with `out_amax` (f16x3 path) returns (output, channel sums float64 (c_out, 2))
         computed in the conv epilogue, and atomicMax'es |output|max into out_amax."""
-        x0 = parts[0]
-        x1 = parts[1] if len(parts) > 1 else None
-        cin0, d, h, w = x0.shape
-        up = 2 if upsample else 1
-        pad = 1 if ksize == 3 else 0
-        od = (d * up + 2 * pad - ksize) // stride + 1
-        oh = (h * up + 2 * pad - ksize) // stride + 1
-        ow = (w * up + 2 * pad - ksize) // stride + 1
-        desc = ConvDesc()
-        if out_size is not None:   # odd-grid crop (diffusion_network.py:925-930): the cropped voxels are never computed
-            od, oh, ow = min(od, int(out_size[0])), min(oh, int(out_size[1])), min(ow, int(out_size[2]))
-            desc.out_d, desc.out_h, desc.out_w = od, oh, ow
-        out = torch.empty((cout, od, oh, ow), device=self.device, dtype=torch.float32)
-        desc.d_in0 = x0.data_ptr(); desc.c0 = cin0
-        desc.d_in1 = x1.data_ptr() if x1 is not None else None
-        desc.c1 = x1.shape[0] if x1 is not None else 0
-        desc.in_d, desc.in_h, desc.in_w = d, h, w
-        desc.upsample = 1 if upsample else 0
-        desc.stride = stride
-        desc.ksize = ksize
-        desc.d_pro_a = pro[0].data_ptr() if pro is not None else None
-        desc.d_pro_b = pro[1].data_ptr() if pro is not None else None
-        desc.d_gamma = affine[0].data_ptr() if affine is not None else None
-        desc.d_beta = affine[1].data_ptr() if affine is not None else None
-        desc.act = act
-        desc.d_w = packed_w.data_ptr() if packed_w is not None else None
-        desc.d_w16 = w16.data_ptr() if w16 is not None else None
-        desc.w16_subpixel = 1 if subpixel else 0
-        desc.d_in_amax0 = in_amax[0].data_ptr() if in_amax else None
-        desc.d_in_amax1 = in_amax[1].data_ptr() if in_amax and len(in_amax) > 1 else None
-        desc.in_bound = float(in_bound)
-        desc.d_bias = bias.data_ptr() if bias is not None else None
-        desc.c_out = cout
-        desc.d_residual = residual.data_ptr() if residual is not None else None
-        desc.d_out = out.data_ptr()
-        if skip is not None:   # folded 1x1x1 skip convolution: dict(parts, w16, bias, amax)
-            sp = skip["parts"]
-            desc.d_skip_in0 = sp[0].data_ptr(); desc.skip_c0 = sp[0].shape[0]
-            desc.d_skip_in1 = sp[1].data_ptr() if len(sp) > 1 else None
-            desc.skip_c1 = sp[1].shape[0] if len(sp) > 1 else 0
-            desc.d_skip_w16 = skip["w16"].data_ptr()
-            desc.d_skip_bias = skip["bias"].data_ptr() if skip["bias"] is not None else None
-            desc.d_skip_amax0 = skip["amax"][0].data_ptr()
-            desc.d_skip_amax1 = skip["amax"][1].data_ptr() if len(sp) > 1 else None
+        desc, out, stats, _ = fill_conv_desc(
+            self.lib, lambda shape, dtype: torch.empty(shape, device=self.device, dtype=dtype), parts, packed_w, bias, cout, ksize,
+            stride=stride, upsample=upsample, pro=pro, affine=affine, act=act, residual=residual, w16=w16, in_amax=in_amax,
+            in_bound=in_bound, out_amax=out_amax, out_size=out_size, skip=skip, subpixel=subpixel, split_k=self.split_k)
         sums = None
-        if w16 is not None and self.split_k:
-            wsb = self.lib.pixie_conv_workspace_bytes(C.byref(desc))
-            if wsb > 0:   # small-output layer: split-K scratch (torch's caching allocator makes this a pointer bump)
-                workspace = torch.empty(wsb, device=self.device, dtype=torch.uint8)
-                desc.d_workspace = workspace.data_ptr()
-        if out_amax is not None and w16 is not None:
-            nfl = self.lib.pixie_conv_stats_floats(C.byref(desc))
-            if nfl > 0:
-                stats = torch.empty(nfl, device=self.device, dtype=torch.float32)
-                desc.d_out_stats = stats.data_ptr()
-                desc.d_out_amax = out_amax.data_ptr()
         if self.record_variant:   # profilers: which kernel instantiation this launch is (grouping key of rocprofv3)
             sl = C.c_int(1)
             self.last_variant = (int(_lib.load(diag=True).pixie_conv_kernel_variant(C.byref(desc), C.byref(sl))), int(sl.value))   # a pure function of the descriptor

@@ -114,7 +114,10 @@ def test_subpixel_upconv_epilogue_statistics(ops, case):
     assert abs(float(slot.view(torch.float32).item()) - float(out.abs().max())) == 0.0
 
 
-@pytest.mark.parametrize("shape", [((256,), 256, (8, 8, 8)), ((256,), 256, (16, 16, 16)), ((128, 128), 128, (4, 4, 4))])
+SUBPIXEL_SPLIT_K_SHAPES = [((256,), 256, (8, 8, 8)), ((256,), 256, (16, 16, 16)), ((128, 128), 128, (4, 4, 4))]
+
+
+@pytest.mark.parametrize("shape", SUBPIXEL_SPLIT_K_SHAPES)
 def test_subpixel_upconv_split_k(ops, shape):
     """The deep up-convs have too few tiles for the chip and split their channel chunks: same result as the unsplit
     launch to fp32 summation-order accuracy, bit-reproducible, no epilogue statistics."""

@@ -229,8 +229,12 @@ def test_conv3d_prologue_variants_on_the_dominant_shape(ops, variant):
         assert rel_l2(got.numpy(), ref.numpy()) < 2e-6
 
 
-@pytest.mark.parametrize("shape", [((64,), 64, (32, 32, 32), 3), ((64, 64), 64, (16, 16, 32), 3), ((64,), 8, (16, 16, 16), 3),
-                                   ((256,), 256, (4, 4, 4), 3), ((128,), 32, (8, 16, 32), 1)])
+# (the case tables of the next three tests have names: tests/test_conv_variant_census.py reads them)
+STATS_SHAPES = [((64,), 64, (32, 32, 32), 3), ((64, 64), 64, (16, 16, 32), 3), ((64,), 8, (16, 16, 16), 3),
+                ((256,), 256, (4, 4, 4), 3), ((128,), 32, (8, 16, 32), 1)]
+
+
+@pytest.mark.parametrize("shape", STATS_SHAPES)
 def test_conv3d_epilogue_statistics(ops, shape):
     """Channel sums / sums of squares / |x|max taken in the f16x3 conv epilogue (per-tile fp32 partials + fp64
     finalize) equal a separate pixie_channel_stats pass over the written tensor."""
@@ -254,8 +258,11 @@ def test_conv3d_epilogue_statistics(ops, shape):
     assert abs(float(slot.view(torch.float32).item()) - float(out.abs().max())) == 0.0
 
 
-@pytest.mark.parametrize("shape", [((256,), 256, (16, 16, 16), 3), ((256, 256), 256, (16, 16, 16), 3), ((128,), 128, (32, 32, 32), 3),
-                                   ((256, 128), 256, (4, 4, 4), 3), ((256,), 256, (8, 8, 8), 1)])
+SPLIT_K_SHAPES = [((256,), 256, (16, 16, 16), 3), ((256, 256), 256, (16, 16, 16), 3), ((128,), 128, (32, 32, 32), 3),
+                  ((256, 128), 256, (4, 4, 4), 3), ((256,), 256, (8, 8, 8), 1)]
+
+
+@pytest.mark.parametrize("shape", SPLIT_K_SHAPES)
 def test_conv3d_split_k(ops, shape):
     """Small-output layers (the 16^3 / 32^3 levels) split their channel chunks over workgroup slices + a fixed-order
     reduction: same result as the unsplit kernel to fp32 summation-order accuracy, bit-reproducible run to run, and no
@@ -281,13 +288,16 @@ def test_conv3d_split_k(ops, shape):
     assert rel_l2(a.cpu().numpy(), ref.cpu().numpy()) < 1e-6
 
 
-@pytest.mark.parametrize("shape", [
+FOLD_SHAPES = [
     # (c_in of the 3^3 conv, skip parts, c_out, dims, residual too, split_k allowed)
     (32, (16, 32), 32, (16, 16, 32), False, True),      # 2 chunks: never a split-K layer
     (64, (64, 64), 64, (64, 64, 64), False, True),      # the decoder shape of the BASELINE network (128 -> 64 blocks), 512 full tiles
     (64, (64, 64), 64, (9, 10, 11), True, False),       # ragged tiles, residual as well
     (32, (48,), 40, (8, 12, 20), False, False),         # single skip tensor, c_out padded to 64
-])
+]
+
+
+@pytest.mark.parametrize("shape", FOLD_SHAPES)
 def test_conv3d_folded_skip_convolution(ops, shape):
     """out = conv3(LN-affine + LeakyReLU (h)) + b + conv1(x) + b_skip in one launch (MyResBlock with a channel change,
     diffusion_network.py:691,696-705) against fp64 F.conv3d of both convolutions, and against the two-launch route."""

@@ -248,14 +248,14 @@ typedef struct pixie_conv_desc {
     float in_bound;
     /* f16x3 path only, optional: statistics of the OUTPUT taken in the epilogue (what the next layer's LayerNorm /
      * GroupNorm and the next f16x3 conv's scaling need), instead of a separate pass over the tensor:
-     *   d_out_stats: pixie_conv_stats_floats(desc) floats of per-tile partial sums, finalised into the
-     *   double[2*c_out] layout of pixie_channel_sums by pixie_stats_finalize; d_out_amax: |out|max (float bits),
-     *   atomicMax'ed (caller zeroes). */
+     *   d_out_stats: pixie_conv_stats_floats(desc) floats of partial sums (per tile in fp32; a split-K launch: per segment
+     *   of its reduce in fp64, so 8-byte aligned), finalised into the double[2*c_out] layout of pixie_channel_sums by
+     *   pixie_stats_finalize or pixie_stats_norm_finalize; d_out_amax: |out|max (float bits), atomicMax'ed (caller zeroes). */
     float* d_out_stats;
     uint32_t* d_out_amax;
     /* f16x3 path only, optional: pixie_conv_workspace_bytes(desc) bytes of device scratch.  With it, layers whose output
      * is too small to fill the chip (the 16^3 / 32^3 levels) split their channel chunks over up to 8 workgroup slices
-     * (deterministic: partial outputs are added in a fixed order); such layers do not produce d_out_stats. */
+     * (deterministic: partial outputs are added in a fixed order); the reduce over the slices then takes d_out_stats. */
     void* d_workspace;
     /* Output extent, 0 = the natural size ((in * (upsample ? 2 : 1) + 2 pad - ksize) / stride + 1).  A smaller value crops
      * the trailing planes / rows / columns: the odd-grid crop h[..., :-1] that MyUNetModel.forward applies to an
@@ -301,6 +301,12 @@ int pixie_conv3d_forward(const pixie_conv_desc* desc, void* stream);
 int64_t pixie_conv_stats_floats(const pixie_conv_desc* desc);
 int64_t pixie_conv_workspace_bytes(const pixie_conv_desc* desc);
 int pixie_stats_finalize(const float* d_stats, const pixie_conv_desc* desc, double* d_sums, void* stream);
+/* pixie_stats_finalize and pixie_norm_finalize (below) in one launch, over the channel concatenation of up to two tensors:
+ * part 0 has desc0->c_out channels, part 1 (optional) c1.  A part given with its d_stats/desc has its partials added into
+ * its d_sums (written); a part with d_stats NULL has final d_sums already (read).  d_a / d_b get c_out + c1 entries. */
+int pixie_stats_norm_finalize(const float* d_stats0, const pixie_conv_desc* desc0, double* d_sums0, const float* d_stats1,
+                              const pixie_conv_desc* desc1, double* d_sums1, int c1, int64_t spatial, int mode, int groups,
+                              double eps, const float* d_weight, const float* d_bias, float* d_a, float* d_b, void* stream);
 /* 1 if this descriptor's launch (its shape fields, d_w16 and d_workspace as they will be passed) can take a folded skip
  * convolution with skip_c0 + skip_c1 input channels; the skip pointers themselves need not be set yet. */
 int pixie_conv_skip_foldable(const pixie_conv_desc* desc);

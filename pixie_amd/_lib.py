@@ -132,6 +132,7 @@ SIGNATURES = {
     "pixie_conv_stats_floats": (_I64, [C.POINTER(ConvDesc)]),
     "pixie_conv_workspace_bytes": (_I64, [C.POINTER(ConvDesc)]),
     "pixie_stats_finalize": (_I, [_VP, C.POINTER(ConvDesc), _VP, _VP]),
+    "pixie_stats_norm_finalize": (_I, [_VP, C.POINTER(ConvDesc), _VP, _VP, C.POINTER(ConvDesc), _VP, _I, _I64, _I, _I, _D, _VP, _VP, _VP, _VP, _VP]),
     "pixie_channel_stats": (_I, [_VP, _I, _I64, _VP, _VP, _VP]),
     "pixie_tensor_amax": (_I, [_VP, _I64, _VP, _VP]),
     "pixie_channel_sums": (_I, [_VP, _I, _I64, _VP, _VP]),

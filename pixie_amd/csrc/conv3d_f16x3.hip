@@ -691,19 +691,79 @@ __global__ __launch_bounds__(256, 2) void conv3d_f16x3_c64_fullres_kernel(Conv16
     conv3d_f16x3_body<3, 2, 4>(A);
 }
 
-// stats[tile][coutp][2] (fp32, from the conv epilogues) -> sums[c][2] (fp64), one workgroup per channel
-__global__ __launch_bounds__(256) void stats_finalize_kernel(const float* __restrict__ stats, int n_tiles, int coutp, double* __restrict__ sums) {
-    const int c = blockIdx.x;
+// Where a producer left the partial statistics of its output: n partials per channel, (sum, sum of squares) pairs; partial t of
+// channel c lies at pair index c * cstride + t * tstride.  The conv epilogues write stats[tile][coutp] in fp32, the split-K
+// reduce writes stats[c][segment] in fp64.  n = 0: the channel's double[2] sums are already final.
+struct StatParts { const void* p; int n; long cstride, tstride; int f64; };
+
+// One workgroup (256 threads) adds the partials of channel c in fp64, in a fixed order: thread t takes partials t, t + 256, ...,
+// then the 64-lane tree, then the four waves.  Every thread returns the totals; r is 8 doubles of LDS, free again on return.
+__device__ inline void block_channel_sums(const StatParts& P, int c, double* r, double& o1, double& o2) {
     double s1 = 0.0, s2 = 0.0;
-    for (int t = threadIdx.x; t < n_tiles; t += 256) {
-        const float2 v = *reinterpret_cast<const float2*>(stats + ((size_t)t * coutp + c) * 2);
-        s1 += v.x; s2 += v.y;
+    for (int t = threadIdx.x; t < P.n; t += 256) {
+        const size_t k = ((size_t)c * P.cstride + (size_t)t * P.tstride) * 2;
+        if (P.f64) { const double2 v = *reinterpret_cast<const double2*>(static_cast<const double*>(P.p) + k); s1 += v.x; s2 += v.y; }
+        else { const float2 v = *reinterpret_cast<const float2*>(static_cast<const float*>(P.p) + k); s1 += v.x; s2 += v.y; }
     }
     for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
-    __shared__ double r[8];
     if ((threadIdx.x & 63) == 0) { r[2 * (threadIdx.x >> 6)] = s1; r[2 * (threadIdx.x >> 6) + 1] = s2; }
     __syncthreads();
-    if (threadIdx.x == 0) { sums[2 * c] = r[0] + r[2] + r[4] + r[6]; sums[2 * c + 1] = r[1] + r[3] + r[5] + r[7]; }
+    o1 = r[0] + r[2] + r[4] + r[6]; o2 = r[1] + r[3] + r[5] + r[7];
+    __syncthreads();
+}
+
+// partial statistics -> sums[c][2] (fp64), one workgroup per channel
+__global__ __launch_bounds__(256) void stats_finalize_kernel(StatParts P, double* __restrict__ sums) {
+    const int c = blockIdx.x;
+    __shared__ double r[8];
+    double s1, s2;
+    block_channel_sums(P, c, r, s1, s2);
+    if (threadIdx.x == 0) { sums[2 * c] = s1; sums[2 * c + 1] = s2; }
+}
+
+// stats_finalize_kernel and norm_finalize_kernel (unet_ops.hip) in one launch: the producers' partials -> the double[2c] sums
+// (kept: a later concatenation reads them again) AND the consumer's per-channel affine (a, b), same arithmetic as
+// norm_finalize_kernel.  The statistics of th.cat([x0, x1]) are channels [0, c0) of part 0 and [c0, channels) of part 1; a part
+// whose sums are final already has P.n = 0.  mode 0: one workgroup per channel; mode 1: one per group, which adds its channels
+// in ascending order.  No workgroup needs another one's result.
+__global__ __launch_bounds__(256) void stats_norm_finalize_kernel(StatParts P0, double* sums0, int c0, StatParts P1, double* sums1, int channels,
+                                                                  double spatial, int mode, int groups, double eps,
+                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                  float* __restrict__ a, float* __restrict__ b) {
+    __shared__ double r[8];
+    const int cpg = mode == 0 ? 1 : channels / groups;
+    const int first = blockIdx.x * cpg;
+    double s1 = 0.0, s2 = 0.0;
+    for (int k = first; k < first + cpg; ++k) {
+        const bool in0 = k < c0;
+        const StatParts& P = in0 ? P0 : P1;
+        double* sums = in0 ? sums0 : sums1;
+        const int kc = in0 ? k : k - c0;
+        double t1, t2;
+        if (P.n > 0) {
+            block_channel_sums(P, kc, r, t1, t2);
+            if (threadIdx.x == 0) { sums[2 * kc] = t1; sums[2 * kc + 1] = t2; }
+        } else {
+            t1 = sums[2 * kc]; t2 = sums[2 * kc + 1];
+        }
+        s1 += t1; s2 += t2;
+    }
+    const double cnt = mode == 0 ? spatial : spatial * cpg;
+    const double mean = s1 / cnt;
+    double var = s2 / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double rstd = 1.0 / sqrt(var + eps);
+    for (int k = first + threadIdx.x; k < first + cpg; k += 256) {
+        if (mode == 0) {
+            a[k] = (float)rstd;
+            b[k] = (float)(-mean * rstd);
+        } else {
+            const double w = weight ? (double)weight[k] : 1.0;
+            const double bb = bias ? (double)bias[k] : 0.0;
+            a[k] = (float)(rstd * w);
+            b[k] = (float)(bb - mean * rstd * w);
+        }
+    }
 }
 
 // out = sum_s partial[s] + bias (+ residual), slices added in a fixed order (deterministic split-K)
@@ -716,6 +776,85 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     if (bias) v += bias[i / osp];
     if (residual) v += residual[i];
     out[i] = v;
+}
+
+// The same reduce where the caller asked for the output's statistics: grid = (segments, c_out), a workgroup owns kReduceSeg
+// consecutive voxels of ONE channel, so the bias is a workgroup constant, and while the stored values are in registers it takes
+// their sum and sum of squares (fp64 from the first addition on) and their |x|max.  Every workgroup overwrites its own slot
+// stats[c][segment][2] -- no floating-point atomics, nothing to zero -- and stats_norm_finalize_kernel adds the segments up.
+// The output is bit-identical to splitk_reduce_kernel's: same slice order, then bias, then residual.
+// |x|max: ONE atomicMax per workgroup, and none where the slot already holds a value as large.  The workgroups of these small
+// layers all reach that point within microseconds of each other, and device-scope atomics on one address are served one after
+// the other (measured: one atomic per wave made this kernel 119 us on average, against 13 us for splitk_reduce_kernel).
+// VEC: osp % 4 == 0 and 16-byte aligned pointers, float4 accesses; otherwise strided scalars.
+constexpr int kReduceSeg = 4096;
+template <bool VEC>
+__global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* __restrict__ partial, int slices, long n_elems, long osp,
+                                                                  const float* __restrict__ bias, const float* residual, float* out,
+                                                                  double* __restrict__ stats, unsigned* out_amax) {
+    const int c = blockIdx.y;
+    const long seg0 = (long)blockIdx.x * kReduceSeg;
+    const size_t base = (size_t)c * osp;
+    const float bv = bias ? bias[c] : 0.0f;
+    double s1 = 0.0, s2 = 0.0;
+    float mx = 0.0f;
+    if (VEC) {
+#pragma unroll
+        for (int k = 0; k < kReduceSeg / 1024; ++k) {
+            const long j = seg0 + k * 1024 + (long)threadIdx.x * 4;
+            if (j < osp) {
+                const size_t i = base + j;
+                float4 v = *reinterpret_cast<const float4*>(partial + i);
+                for (int s = 1; s < slices; ++s) {
+                    const float4 q = *reinterpret_cast<const float4*>(partial + (size_t)s * n_elems + i);
+                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+                }
+                if (bias) { v.x += bv; v.y += bv; v.z += bv; v.w += bv; }
+                if (residual) {
+                    const float4 q = *reinterpret_cast<const float4*>(residual + i);
+                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+                }
+                *reinterpret_cast<float4*>(out + i) = v;
+                const double x = v.x, y = v.y, z = v.z, w = v.w;
+                s1 += (x + y) + (z + w);
+                s2 += (x * x + y * y) + (z * z + w * w);
+                mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int k = 0; k < kReduceSeg / 256; ++k) {
+            const long j = seg0 + k * 256 + threadIdx.x;
+            if (j < osp) {
+                const size_t i = base + j;
+                float v = partial[i];
+                for (int s = 1; s < slices; ++s) v += partial[(size_t)s * n_elems + i];
+                if (bias) v += bv;
+                if (residual) v += residual[i];
+                out[i] = v;
+                const double x = v;
+                s1 += x; s2 += x * x; mx = fmaxf(mx, fabsf(v));
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+        mx = fmaxf(mx, __shfl_down(mx, off, 64));
+    }
+    __shared__ double r[8];
+    __shared__ float rmx[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { r[2 * wave] = s1; r[2 * wave + 1] = s2; rmx[wave] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* dst = stats + ((size_t)c * gridDim.x + blockIdx.x) * 2;
+        dst[0] = r[0] + r[2] + r[4] + r[6];
+        dst[1] = r[1] + r[3] + r[5] + r[7];
+        const unsigned m = __float_as_uint(fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3])));
+        // the slot only grows: a stale read can only be too small, and then costs the atomic it would have cost anyway
+        if (out_amax && m > __hip_atomic_load(out_amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out_amax, m);
+    }
 }
 
 // |x|max of a tensor as float bits (non-negative floats order like unsigned integers); caller zeroes the slot
@@ -918,6 +1057,21 @@ static void conv16_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, 
     MB_out = MB; NB_out = NB;
 }
 
+// split-K launches: segments per channel of splitk_reduce_stats_kernel = partial statistics per channel
+static int reduce_segments(long osp) { return (int)((osp + kReduceSeg - 1) / kReduceSeg); }
+
+// where the launch of this descriptor leaves its partial statistics (d_out_stats): per tile in fp32, or per reduce segment in fp64
+static StatParts conv16_stat_parts(const pixie_conv_desc* d, const void* stats) {
+    Conv16Args a{};
+    int MB = 0, NB = 0, slices = 1;
+    conv16_tiling(d, a, MB, NB, &slices);
+    if (slices > 1) {
+        const int n = reduce_segments((long)a.OD * a.OH * a.OW);
+        return StatParts{stats, n, n, 1, 1};
+    }
+    return StatParts{stats, a.n_tiles, 1, a.coutp, 0};
+}
+
 // LDS the transposing epilogue needs (4 waves x 32 rows x (NB*32 + 4) floats + the statistics partials), and whether a launch
 // gets it: unsplit launches only, as long as two workgroups still fit on a CU.  One decision for both launchers and for
 // pixie_conv_tile_geometry.
@@ -972,7 +1126,7 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
     if (slices > 1) {
         a.partial = static_cast<float*>(d->d_workspace);
         a.chunks_per_slice = (cin / 16 + slices - 1) / slices;
-        a.stats = nullptr; a.out_amax = nullptr;   // pixie_conv_stats_floats reports 0 for these layers
+        a.stats = nullptr; a.out_amax = nullptr;   // the conv kernel writes raw slices; the reduce takes the statistics
     }
 
     size_t lds = (size_t)4 * a.CS * sizeof(uint4);
@@ -992,8 +1146,19 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
         }
         if (rc) return rc;
         const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, slices, n_elems, osp,
-                           a.bias, a.residual, a.out);
+        if (d->d_out_stats) {
+            const dim3 rgrid((unsigned)reduce_segments(osp), (unsigned)a.cout);
+            double* rstats = reinterpret_cast<double*>(d->d_out_stats);
+            PX_REQUIRE((reinterpret_cast<size_t>(rstats) & 7) == 0, "f16x3 conv: d_out_stats of a split-K launch must be 8-byte aligned");
+            const bool vec = osp % 4 == 0 && ((reinterpret_cast<size_t>(a.partial) | reinterpret_cast<size_t>(a.residual) | reinterpret_cast<size_t>(a.out)) & 15) == 0;
+            if (vec) hipLaunchKernelGGL(splitk_reduce_stats_kernel<true>, rgrid, dim3(256), 0, st, a.partial, slices, n_elems, osp, a.bias, a.residual,
+                                        a.out, rstats, d->d_out_amax);
+            else hipLaunchKernelGGL(splitk_reduce_stats_kernel<false>, rgrid, dim3(256), 0, st, a.partial, slices, n_elems, osp, a.bias, a.residual,
+                                    a.out, rstats, d->d_out_amax);
+        } else {
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, slices, n_elems, osp,
+                               a.bias, a.residual, a.out);
+        }
         PX_CHECK_HIP(hipGetLastError());
         return 0;
     }
@@ -1066,7 +1231,8 @@ extern "C" int64_t pixie_conv_stats_floats(const pixie_conv_desc* d) {
     Conv16Args a{};
     int MB = 0, NB = 0, slices = 1;
     conv16_tiling(d, a, MB, NB, &slices);
-    return slices > 1 ? 0 : (int64_t)a.n_tiles * a.coutp * 2;
+    if (slices > 1) return (int64_t)a.cout * reduce_segments((long)a.OD * a.OH * a.OW) * 2 * (int64_t)(sizeof(double) / sizeof(float));
+    return (int64_t)a.n_tiles * a.coutp * 2;
 }
 
 // bytes of d_workspace this layer can use for split-K (0: it would not split).  Decided on the shape alone.
@@ -1127,11 +1293,26 @@ extern "C" int pixie_conv_skip_foldable(const pixie_conv_desc* d) {
 
 extern "C" int pixie_stats_finalize(const float* d_stats, const pixie_conv_desc* d, double* d_sums, void* stream) {
     PX_REQUIRE(d_stats && d && d_sums, "pixie_stats_finalize: null argument");
-    // recompute the tile count exactly as conv3d_f16x3_forward does
-    Conv16Args a{};
-    int MB = 0, NB = 0;
-    conv16_tiling(d, a, MB, NB);
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), d_stats, a.n_tiles, a.coutp, d_sums);
+    // the tile (or segment) count is recomputed exactly as conv3d_f16x3_forward computes it
+    hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), conv16_stat_parts(d, d_stats), d_sums);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pixie_stats_norm_finalize(const float* d_stats0, const pixie_conv_desc* desc0, double* d_sums0, const float* d_stats1,
+                                         const pixie_conv_desc* desc1, double* d_sums1, int c1, int64_t spatial, int mode, int groups,
+                                         double eps, const float* d_weight, const float* d_bias, float* d_a, float* d_b, void* stream) {
+    PX_REQUIRE(desc0 && d_sums0 && d_a && d_b && spatial > 0 && c1 >= 0, "pixie_stats_norm_finalize: bad arguments");
+    PX_REQUIRE(c1 == 0 || d_sums1, "pixie_stats_norm_finalize: a second part needs d_sums1");
+    PX_REQUIRE(!d_stats1 || desc1, "pixie_stats_norm_finalize: d_stats1 needs its descriptor");
+    const int c0 = desc0->c_out, channels = c0 + c1;
+    PX_REQUIRE(!d_stats1 || desc1->c_out == c1, "pixie_stats_norm_finalize: desc1 has %d output channels, c1 is %d", desc1 ? desc1->c_out : 0, c1);
+    PX_REQUIRE(mode == 0 || (mode == 1 && groups > 0 && channels % groups == 0), "pixie_stats_norm_finalize: bad mode/groups");
+    const StatParts none{nullptr, 0, 0, 0, 0};
+    const StatParts p0 = d_stats0 ? conv16_stat_parts(desc0, d_stats0) : none;
+    const StatParts p1 = d_stats1 ? conv16_stat_parts(desc1, d_stats1) : none;
+    hipLaunchKernelGGL(stats_norm_finalize_kernel, dim3((unsigned)(mode == 0 ? channels : groups)), dim3(256), 0, as_stream(stream), p0, d_sums0, c0,
+                       p1, d_sums1, channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -234,6 +234,10 @@ struct Tens {
     int64_t sums_off = -1;        // arena range of `sums` when a conv epilogue produced them (-1: pre-zeroed region, or none yet)
     bool has_sums = false;        // double[2c] channel sums of this tensor exist (somebody needed them)
     double* sums = nullptr;
+    // the producing conv left partial statistics (pixie_conv_desc.d_out_stats) that nobody has added up yet: the first
+    // normalisation that reads the tensor does, in the launch that also makes its affine (pixie_stats_norm_finalize)
+    int64_t partials_off = -1;
+    pixie_conv_desc pdesc;
     uint32_t* slot = nullptr;     // |x|max as float bits
     int64_t spatial() const { return (int64_t)d * h * w; }
     ~Tens();
@@ -260,6 +264,7 @@ struct pixie_unet {
     std::vector<uint32_t> h_bound_slots;
     std::map<std::tuple<int, int, int, bool>, Sized> sized;   // (d, h, w, starts behind projector.net[0]) -> what one pass needs
     bool fuse_stats = true, split_k = true, fold_skip = true, subpixel = true;
+    bool split_stats = true;               // split-K layers take their output's statistics in the reduce (PIXIE_SPLIT_STATS=0: a separate pass)
     // pixie_unet_set_option("graph", 1): forward() replays a captured HIP graph when called again with the same pointers
     struct Replay { const float* feat; const float* proj0; float* out; void* ws; int d; uint64_t epoch; hipGraph_t graph; hipGraphExec_t exec; };
     bool use_graph = false;
@@ -363,8 +368,8 @@ struct Exec {
     }
 
     // ---- statistics ----
-    void stats(const TP& t) {                  // channel sums + |x|max by a pass over the tensor (only where no conv epilogue produced them)
-        if (t->has_sums) return;
+    void stats(const TP& t) {                  // channel sums + |x|max by a pass over the tensor (only where no conv produced them)
+        if (t->has_sums || t->partials_off >= 0) return;
         t->has_sums = true;
         if (!dry && zsum_next + 2 * t->c > zsum_cap) fail("pixie_unet_forward: out of statistics space (internal sizing error)");
         t->sums = dry ? nullptr : zsums + zsum_next;      // the kernel adds into zeroed memory (fp64 atomics)
@@ -373,13 +378,33 @@ struct Exec {
         if (!dry) ok(channel_stats_prezeroed(t->p, t->c, t->spatial(), t->sums, t->slot, as_stream(stream)), "pixie_channel_stats");
     }
     struct AB { std::shared_ptr<Scratch> mem; float* a; float* b; };
-    AB norm_finalize(const double* sums, int c, int64_t spatial, int mode, int groups, const float* w, const float* b) {
+    // The prologue affine of a normalisation over th.cat(parts) (never materialised; statistics are read where they lie).
+    // ONE launch: a part whose producer left partial statistics has them added up into its double[2c] sums here as well.
+    AB norm_finalize(const std::vector<TP>& parts, int64_t spatial, int mode, int groups, const float* w, const float* b) {
+        for (auto& t : parts) stats(t);
+        const Tens* t0 = parts[0].get();
+        const Tens* t1 = parts.size() > 1 ? parts[1].get() : nullptr;
+        const int c0 = t0->c, c1 = t1 ? t1->c : 0, c = c0 + c1;
         AB r;
         const int cpad = (c + 63) / 64 * 64;
         r.mem = std::make_shared<Scratch>(this, (int64_t)(cpad + c) * sizeof(float));
         r.a = r.mem->as<float>();
         r.b = r.a + cpad;
-        if (!dry) ok(pixie_norm_finalize(sums, c, spatial, mode, groups, 1e-5, w, b, r.a, r.b, stream), "pixie_norm_finalize");
+        const bool p0 = t0->partials_off >= 0, p1 = t1 && t1->partials_off >= 0;
+        if (p0 || p1) {
+            // (part 0 carries the descriptor that tells its channel count even where its sums are final)
+            pixie_conv_desc d0 = t0->pdesc;
+            if (!p0) { std::memset(&d0, 0, sizeof d0); d0.c_out = c0; }
+            if (!dry) ok(pixie_stats_norm_finalize(p0 ? arena.ptr<float>(t0->partials_off) : nullptr, &d0, t0->sums,
+                                                   p1 ? arena.ptr<float>(t1->partials_off) : nullptr, p1 ? &t1->pdesc : nullptr, t1 ? t1->sums : nullptr,
+                                                   c1, spatial, mode, groups, 1e-5, w, b, r.a, r.b, stream), "pixie_stats_norm_finalize");
+            for (auto& t : parts)
+                if (t->partials_off >= 0) { arena.release(t->partials_off); t->partials_off = -1; t->has_sums = true; }   // stream order: free at once
+        } else if (!t1) {
+            if (!dry) ok(pixie_norm_finalize(t0->sums, c, spatial, mode, groups, 1e-5, w, b, r.a, r.b, stream), "pixie_norm_finalize");
+        } else {
+            if (!dry) ok(norm_finalize_cat(t0->sums, c0, t1->sums, c1, spatial, mode, groups, 1e-5, w, b, r.a, r.b, as_stream(stream)), "pixie_norm_finalize");
+        }
         return r;
     }
 
@@ -463,7 +488,7 @@ struct Exec {
             desc.in_bound = o.bound;
         }
         // sizes of the optional buffers depend on the shape fields only; the dry run needs non-null placeholders for them
-        std::unique_ptr<Scratch> workspace, tile_stats;
+        std::unique_ptr<Scratch> workspace;
         if (dry) { desc.d_w16 = reinterpret_cast<const void*>(0x100); }
         if (net->split_k) {
             const int64_t wsb = pixie_conv_workspace_bytes(&desc);
@@ -474,46 +499,31 @@ struct Exec {
             // the output's channel sums and |x|max come out of the conv epilogue: no separate pass over the tensor
             uint32_t* slot = new_slot();
             const int64_t nfl = pixie_conv_stats_floats(&desc);
-            if (nfl > 0) {
-                tile_stats.reset(new Scratch(this, nfl * (int64_t)sizeof(float)));
-                desc.d_out_stats = tile_stats->as<float>();
+            if (nfl > 0 && (!workspace || net->split_stats)) {   // (split-K layers too: their reduce takes the statistics)
+                out->partials_off = arena.alloc(nfl * (int64_t)sizeof(float));
+                desc.d_out_stats = arena.ptr<float>(out->partials_off);
                 desc.d_out_amax = slot;
                 have_stats = true;
                 out->slot = slot;
             }
         }
         if (!dry) ok(pixie_conv3d_forward(&desc, stream), "pixie_conv3d_forward");
-        if (have_stats) {
+        if (have_stats) {   // the partials stay until a normalisation reads the tensor (norm_finalize); if none does, nothing adds them up
             out->sums_off = arena.alloc((int64_t)cout * 2 * sizeof(double));
             out->sums = arena.ptr<double>(out->sums_off);
-            out->has_sums = true;
-            if (!dry) ok(pixie_stats_finalize(desc.d_out_stats, &desc, out->sums, stream), "pixie_stats_finalize");
+            out->pdesc = desc;
         }
         return out;
     }
 
     // ---- blocks ----
-    AB norm_finalize_parts(const std::vector<TP>& parts, int64_t spatial) {   // LayerNorm statistics of th.cat(parts): read where they lie
-        for (auto& t : parts) stats(t);
-        if (parts.size() == 1) return norm_finalize(parts[0]->sums, parts[0]->c, spatial, 0, 1, nullptr, nullptr);
-        const int c0 = parts[0]->c, c1 = parts[1]->c, c = c0 + c1;
-        AB r;
-        const int cpad = (c + 63) / 64 * 64;
-        r.mem = std::make_shared<Scratch>(this, (int64_t)(cpad + c) * sizeof(float));
-        r.a = r.mem->as<float>();
-        r.b = r.a + cpad;
-        if (!dry) ok(norm_finalize_cat(parts[0]->sums, c0, parts[1]->sums, c1, spatial, 0, 1, 1e-5, nullptr, nullptr, r.a, r.b, as_stream(stream)),
-                     "pixie_norm_finalize");
-        return r;
-    }
     TP res(const Blk& b, const std::vector<TP>& parts) {   // MyResBlock.forward, diffusion_network.py:696-705
         const std::string& p = b.prefix;
         const int64_t spatial = parts[0]->spatial();
-        AB pro = norm_finalize_parts(parts, spatial);
+        AB pro = norm_finalize(parts, spatial, 0, 1, nullptr, nullptr);
         ConvOpt o1; o1.pro = &pro; o1.affine_store = p + ".in_layers.0"; o1.act = ACT_LEAKY; o1.bound = norm_bound(p + ".in_layers.0", spatial);
         TP h = conv(parts, p + ".in_layers.2", b.cout, 3, o1);
-        stats(h);
-        AB pro2 = norm_finalize(h->sums, b.cout, spatial, 0, 1, nullptr, nullptr);
+        AB pro2 = norm_finalize({h}, spatial, 0, 1, nullptr, nullptr);
         TP skip = parts[0];
         ConvOpt o2; o2.pro = &pro2; o2.affine_store = p + ".out_layers.0"; o2.act = ACT_LEAKY; o2.bound = norm_bound(p + ".out_layers.0", spatial);
         if (b.cin != b.cout) {
@@ -534,8 +544,7 @@ struct Exec {
         const std::string& p = b.prefix;
         const int c = x->c;
         const int64_t spatial = x->spatial();
-        stats(x);
-        AB pro = norm_finalize(x->sums, c, spatial, 1, 32, P(p + ".norm.weight"), P(p + ".norm.bias"));
+        AB pro = norm_finalize({x}, spatial, 1, 32, P(p + ".norm.weight"), P(p + ".norm.bias"));
         ConvOpt o; o.pro = &pro; o.bound = norm_bound(p + ".norm", spatial * (c / 32));
         TP qkv = conv({x}, p + ".qkv", 3 * c, 1, o);
         TP att = make(c, x->d, x->h, x->w);
@@ -571,23 +580,19 @@ struct Exec {
             if (!hid) {
                 const int g = std::max(c.cond_dim / 2, 1);
                 x = conv({external(d_feat, c.feature_channels, D, H, W)}, q + "0", c.cond_dim, 1, ConvOpt{});
-                stats(x);
-                pro_in = norm_finalize(x->sums, c.cond_dim, spatial, 1, g, P(q + "1.weight"), P(q + "1.bias"));
+                pro_in = norm_finalize({x}, spatial, 1, g, P(q + "1.weight"), P(q + "1.bias"));
                 act_in = ACT_SILU;
                 bound_in = norm_bound(q + "1", spatial * (c.cond_dim / g));
             } else {
                 if (d_proj0) x = external(d_proj0, hid, D, H, W);
                 else x = conv({external(d_feat, c.feature_channels, D, H, W)}, q + "0", hid, 1, ConvOpt{});
-                stats(x);
-                AB pro = norm_finalize(x->sums, hid, spatial, 1, 32, P(q + "1.weight"), P(q + "1.bias"));
+                AB pro = norm_finalize({x}, spatial, 1, 32, P(q + "1.weight"), P(q + "1.bias"));
                 ConvOpt o; o.pro = &pro; o.act = ACT_SILU; o.bound = norm_bound(q + "1", spatial * (hid / 32));
                 x = conv({x}, q + "3", hid, 3, o);
-                stats(x);
-                AB pro2 = norm_finalize(x->sums, hid, spatial, 1, 32, P(q + "4.weight"), P(q + "4.bias"));
+                AB pro2 = norm_finalize({x}, spatial, 1, 32, P(q + "4.weight"), P(q + "4.bias"));
                 ConvOpt o2; o2.pro = &pro2; o2.act = ACT_SILU; o2.bound = norm_bound(q + "4", spatial * (hid / 32));
                 x = conv({x}, q + "6", c.cond_dim, 1, o2);
-                stats(x);
-                pro_in = norm_finalize(x->sums, c.cond_dim, spatial, 1, 32, P(q + "7.weight"), P(q + "7.bias"));
+                pro_in = norm_finalize({x}, spatial, 1, 32, P(q + "7.weight"), P(q + "7.bias"));
                 bound_in = norm_bound(q + "7", spatial * std::max(c.cond_dim / 32, 1));
             }
             pro_in_p = &pro_in;
@@ -619,8 +624,7 @@ struct Exec {
             }
             h = parts[0];
         }
-        stats(h);
-        AB pro = norm_finalize(h->sums, h->c, h->spatial(), 0, 1, nullptr, nullptr);
+        AB pro = norm_finalize({h}, h->spatial(), 0, 1, nullptr, nullptr);
         ConvOpt oo; oo.pro = &pro; oo.affine_store = "unet.out.0"; oo.act = ACT_LEAKY; oo.bound = norm_bound("unet.out.0", h->spatial());
         oo.out_ptr = d_out;
         return conv({h}, "unet.out.2", c.out_channels, 3, oo);
@@ -631,6 +635,7 @@ Tens::~Tens() {
     if (!ex) return;
     if (off >= 0) ex->arena.release(off);
     if (sums_off >= 0) ex->arena.release(sums_off);
+    if (partials_off >= 0) ex->arena.release(partials_off);
 }
 
 // max|weight| and max|bias| of every normalisation layer whose parameters changed: device reductions, ONE copy, ONE
@@ -724,6 +729,7 @@ extern "C" int pixie_unet_create(pixie_unet** out, const pixie_unet_config* c) {
         const char* fs = getenv("PIXIE_FUSE_STATS"); n->fuse_stats = !(fs && fs[0] == '0');
         const char* sk = getenv("PIXIE_CONV_SPLIT_K"); n->split_k = !(sk && sk[0] == '0');
         const char* fk = getenv("PIXIE_FOLD_SKIP"); n->fold_skip = !(fk && fk[0] == '0');
+        const char* ss = getenv("PIXIE_SPLIT_STATS"); n->split_stats = !(ss && ss[0] == '0');
         const char* sx = getenv("PIXIE_CONV_SUBPIXEL"); n->subpixel = !(sx && sx[0] == '0');
         *out = n.release();
         return 0;

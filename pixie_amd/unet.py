@@ -51,10 +51,10 @@ def _addr(t: Optional[torch.Tensor]):
 def fill_conv_desc(lib, alloc, parts: Sequence[torch.Tensor], packed_w, bias, cout: int, ksize: int, *, stride: int = 1,
                    upsample: bool = False, pro=None, affine=None, act: int = 0, residual=None, w16=None, in_amax=None,
                    in_bound: float = 0.0, out_amax=None, out_size=None, skip=None, subpixel: bool = False, split_k: bool = True,
-                   addr=_addr):
+                   split_stats: bool = False, addr=_addr):
     """The pixie_conv_desc of one convolution launch, as HipOps.conv issues it: geometry, operands, the split-K workspace where
     the library says the layer splits (f16x3 path, `split_k`) and the epilogue-statistics buffer where `out_amax` asks for one
-    and the layer has one.  `alloc(shape, dtype)` makes the output / workspace / statistics tensors, `addr(tensor)` is their
+    and the layer has one (a split-K layer: only with `split_stats`, its reduce then takes them).  `alloc(shape, dtype)` makes the output / workspace / statistics tensors, `addr(tensor)` is their
     address: the product passes device tensors; a test that only wants to know WHAT would be launched passes shape-only
     tensors and a non-null stand-in address (no field is dereferenced here).  Returns (desc, out, stats, workspace)."""
     x0 = parts[0]
@@ -109,11 +109,19 @@ def fill_conv_desc(lib, alloc, parts: Sequence[torch.Tensor], packed_w, bias, co
             desc.d_workspace = addr(workspace)
     if out_amax is not None and w16 is not None:
         nfl = lib.pixie_conv_stats_floats(C.byref(desc))
-        if nfl > 0:
+        if nfl > 0 and (workspace is None or split_stats):
             stats = alloc((nfl,), torch.float32)
             desc.d_out_stats = addr(stats)
             desc.d_out_amax = addr(out_amax)
     return desc, out, stats, workspace
+
+
+class PendingStats:
+    """Partial channel statistics a convolution left behind (pixie_conv_desc.d_out_stats) and that nothing has added up yet;
+    HipOps.stats_norm_finalize does, in the launch that also makes the consumer's affine (unet_exec.hip: Tens::partials_off)."""
+
+    def __init__(self, stats: torch.Tensor, desc: ConvDesc, cout: int):
+        self.stats, self.desc, self.cout = stats, desc, cout
 
 
 class HipOps:
@@ -179,21 +187,26 @@ class HipOps:
              residual: Optional[torch.Tensor] = None, w16: Optional[torch.Tensor] = None,
              in_amax: Optional[Sequence[torch.Tensor]] = None, in_bound: float = 0.0,
              out_amax: Optional[torch.Tensor] = None, out_size: Optional[Tuple[int, int, int]] = None,
-             skip: Optional[dict] = None, subpixel: bool = False):
+             skip: Optional[dict] = None, subpixel: bool = False, defer_stats: bool = False, split_stats: bool = True):
         """`subpixel`: w16 comes from pack_conv_subpixel (upsample, 3^3, stride 1 only).  Returns the output tensor; with `out_amax` (f16x3 path) returns (output, channel sums float64 (c_out, 2))
-        computed in the conv epilogue, and atomicMax'es |output|max into out_amax."""
+        computed in the conv epilogue, and atomicMax'es |output|max into out_amax.  `defer_stats` (the runner): split-K layers
+        take the statistics too, in their reduce (unless `split_stats` is False), and the second value is a PendingStats for
+        stats_norm_finalize."""
         desc, out, stats, _ = fill_conv_desc(
             self.lib, lambda shape, dtype: torch.empty(shape, device=self.device, dtype=dtype), parts, packed_w, bias, cout, ksize,
             stride=stride, upsample=upsample, pro=pro, affine=affine, act=act, residual=residual, w16=w16, in_amax=in_amax,
-            in_bound=in_bound, out_amax=out_amax, out_size=out_size, skip=skip, subpixel=subpixel, split_k=self.split_k)
+            in_bound=in_bound, out_amax=out_amax, out_size=out_size, skip=skip, subpixel=subpixel, split_k=self.split_k,
+            split_stats=defer_stats and split_stats)
         sums = None
         if self.record_variant:   # profilers: which kernel instantiation this launch is (grouping key of rocprofv3)
             sl = C.c_int(1)
             self.last_variant = (int(_lib.load(diag=True).pixie_conv_kernel_variant(C.byref(desc), C.byref(sl))), int(sl.value))   # a pure function of the descriptor
         check(self.lib.pixie_conv3d_forward(C.byref(desc), self.stream), "pixie_conv3d_forward")
         if desc.d_out_stats:
-            sums = torch.empty((cout, 2), device=self.device, dtype=torch.float64)
-            check(self.lib.pixie_stats_finalize(_ptr(stats), C.byref(desc), _ptr(sums), self.stream), "pixie_stats_finalize")
+            if defer_stats:
+                sums = PendingStats(stats, desc, cout)
+            else:
+                sums = self.stats_finalize(PendingStats(stats, desc, cout))
         if out_amax is not None:
             return out, sums
         return out
@@ -234,6 +247,34 @@ class HipOps:
         check(self.lib.pixie_norm_finalize(_ptr(sums), c, spatial, mode, groups, eps, _ptr(weight), _ptr(bias), _ptr(a), _ptr(b),
                                            self.stream), "pixie_norm_finalize")
         return a, b
+
+    def stats_finalize(self, pending: PendingStats) -> torch.Tensor:
+        sums = torch.empty((pending.cout, 2), device=self.device, dtype=torch.float64)
+        check(self.lib.pixie_stats_finalize(_ptr(pending.stats), C.byref(pending.desc), _ptr(sums), self.stream), "pixie_stats_finalize")
+        return sums
+
+    def stats_norm_finalize(self, parts: Sequence, spatial: int, mode: int, groups: int = 1, eps: float = 1e-5,
+                            weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        """norm_finalize over the channel concatenation of one or two tensors' statistics, each either final sums (c, 2) or a
+        PendingStats, whose partials are added up in the same launch.  Returns (a, b, [final sums per part])."""
+        pend = [isinstance(p, PendingStats) for p in parts]
+        sums = [torch.empty((p.cout, 2), device=self.device, dtype=torch.float64) if is_p else p for p, is_p in zip(parts, pend)]
+        c0 = sums[0].shape[0]
+        c1 = sums[1].shape[0] if len(parts) > 1 else 0
+        if pend[0]:
+            desc0 = parts[0].desc
+        else:
+            desc0 = ConvDesc()
+            desc0.c_out = c0
+        two = len(parts) > 1
+        a = torch.empty(c0 + c1, device=self.device, dtype=torch.float32)
+        b = torch.empty(c0 + c1, device=self.device, dtype=torch.float32)
+        check(self.lib.pixie_stats_norm_finalize(
+            _ptr(parts[0].stats) if pend[0] else None, C.byref(desc0), _ptr(sums[0]),
+            _ptr(parts[1].stats) if two and pend[1] else None, C.byref(parts[1].desc) if two and pend[1] else None,
+            _ptr(sums[1]) if two else None, c1, spatial, mode, groups, eps, _ptr(weight), _ptr(bias), _ptr(a), _ptr(b), self.stream),
+            "pixie_stats_norm_finalize")
+        return a, b, sums
 
     def attention(self, qkv: torch.Tensor, channels: int, tokens: int) -> torch.Tensor:
         out = torch.empty((channels, tokens), device=self.device, dtype=torch.float32)
@@ -281,6 +322,7 @@ class UNetRunner:
         self.fuse_stats = os.environ.get("PIXIE_FUSE_STATS", "1") != "0"   # channel statistics in the conv epilogue
         self.fold_skip = os.environ.get("PIXIE_FOLD_SKIP", "1") != "0"     # skip_connection 1x1x1 inside the block's second conv
         self.subpixel = os.environ.get("PIXIE_CONV_SUBPIXEL", "1") != "0"  # up-convs as 8 parities x 2^3 taps over the stored tensor
+        self.split_stats = os.environ.get("PIXIE_SPLIT_STATS", "1") != "0"  # split-K layers: statistics in the reduce, not a separate pass
 
     @property
     def _f16x3(self) -> bool:
@@ -350,13 +392,34 @@ class UNetRunner:
                 self._remember(cache, t, self.ops.channel_stats(t, slot), slot)
             else:
                 self._remember(cache, t, self.ops.channel_sums(t), None)
+        if isinstance(cache[k][0], PendingStats):   # somebody wants the sums alone
+            cache[k] = (self.ops.stats_finalize(cache[k][0]), cache[k][1])
         return cache[k]
+
+    def _norm(self, cache: dict, parts: List[torch.Tensor], spatial: int, mode: int, groups: int = 1, weight=None, bias=None):
+        """The prologue affine of a normalisation over th.cat(parts), from the tensors' statistics (unet_exec.hip:
+        Exec::norm_finalize).  One launch: partial statistics a producer left behind are added up in it."""
+        ops = self.ops
+        for t in parts:
+            if id(t) not in cache:
+                self._stats(cache, t)
+        ents = [cache[id(t)][0] for t in parts]
+        if any(isinstance(e, PendingStats) for e in ents):
+            a, b, sums = ops.stats_norm_finalize(ents, spatial, mode, groups=groups, weight=weight, bias=bias)
+            for t, sm in zip(parts, sums):
+                cache[id(t)] = (sm, cache[id(t)][1])
+            return a, b
+        sums = torch.cat(ents, dim=0) if len(ents) > 1 else ents[0]
+        if mode == 0:
+            return ops.norm_finalize(sums, spatial, 0)
+        return ops.norm_finalize(sums, spatial, mode, groups=groups, weight=weight, bias=bias)
 
     def _sums(self, cache: dict, t: torch.Tensor) -> torch.Tensor:
         return self._stats(cache, t)[0]
 
     def _amax(self, cache: dict, t: torch.Tensor) -> torch.Tensor:
-        return self._stats(cache, t)[1]
+        k = id(t)
+        return cache[k][1] if k in cache else self._stats(cache, t)[1]
 
     def _conv(self, cache: dict, parts: List[torch.Tensor], wkey: str, cout: int, ksize: int, *, stride: int = 1,
               upsample: bool = False, pro=None, affine_key: Optional[str] = None, act: int = ACT_NONE,
@@ -383,6 +446,9 @@ class UNetRunner:
         if self.fuse_stats:
             # the output's channel sums and |x|max come out of the conv epilogue: no separate pass over the tensor
             slot = self._new_slot(cache, parts[0].device)
+            if hasattr(ops, "stats_norm_finalize"):   # (injected reference operators finalise in the convolution)
+                kw["defer_stats"] = True
+                kw["split_stats"] = self.split_stats
             out, sums = ops.conv(parts, None, self._b(wkey), cout, ksize, stride=stride, upsample=upsample, pro=pro, affine=affine,
                                  act=act, residual=residual, w16=self._w16(wkey, sub), out_amax=slot, **kw)
             if sums is not None:
@@ -396,11 +462,10 @@ class UNetRunner:
         """MyResBlock.forward, diffusion_network.py:696-705"""
         ops, p = self.ops, b.prefix
         spatial = parts[0][0].numel()
-        sums = torch.cat([self._sums(cache, t) for t in parts], dim=0) if len(parts) > 1 else self._sums(cache, parts[0])
-        pro = ops.norm_finalize(sums, spatial, 0)
+        pro = self._norm(cache, parts, spatial, 0)
         h = self._conv(cache, parts, p + ".in_layers.2", b.cout, 3, pro=pro, affine_key=p + ".in_layers.0", act=ACT_LEAKY,
                        bound=self._norm_bound(p + ".in_layers.0", spatial))
-        pro2 = ops.norm_finalize(self._sums(cache, h), spatial, 0)
+        pro2 = self._norm(cache, [h], spatial, 0)
         fold = None
         if b.cin != b.cout:
             if (self.fold_skip and self._f16x3 and ops.f16x3_ok([h], 1) and ops.f16x3_ok(parts, 1)
@@ -422,8 +487,7 @@ class UNetRunner:
         ops, p = self.ops, b.prefix
         c = x.shape[0]
         spatial = x[0].numel()
-        pro = ops.norm_finalize(self._sums(cache, x), spatial, 1, groups=32, weight=self.p[p + ".norm.weight"],
-                                bias=self.p[p + ".norm.bias"])
+        pro = self._norm(cache, [x], spatial, 1, groups=32, weight=self.p[p + ".norm.weight"], bias=self.p[p + ".norm.bias"])
         qkv = self._conv(cache, [x], p + ".qkv", 3 * c, 1, pro=pro, bound=self._norm_bound(p + ".norm", spatial * (c // 32)))
         att = ops.attention(qkv.reshape(3 * c, spatial), c, spatial).reshape(x.shape)
         return self._conv(cache, [att], p + ".proj_out", c, 1, residual=x)
@@ -455,25 +519,24 @@ class UNetRunner:
             if cfg.projector_hidden is None:
                 g = max(cfg.cond_dim // 2, 1)
                 x = self._conv(cache, [x], q + "0", cfg.cond_dim, 1)
-                pro_in = ops.norm_finalize(self._sums(cache, x), spatial, 1, groups=g,
-                                           weight=self.p[q + "1.weight"], bias=self.p[q + "1.bias"])
+                pro_in = self._norm(cache, [x], spatial, 1, groups=g, weight=self.p[q + "1.weight"], bias=self.p[q + "1.bias"])
                 act_in = ACT_SILU
                 bound_in = self._norm_bound(q + "1", spatial * (cfg.cond_dim // g))
             else:
                 hid = cfg.projector_hidden
                 x = proj0 if proj0 is not None else self._conv(cache, [x], q + "0", hid, 1)
-                pro = ops.norm_finalize(self._sums(cache, x), spatial, 1, groups=32, weight=self.p[q + "1.weight"], bias=self.p[q + "1.bias"])
+                pro = self._norm(cache, [x], spatial, 1, groups=32, weight=self.p[q + "1.weight"], bias=self.p[q + "1.bias"])
                 x = self._conv(cache, [x], q + "3", hid, 3, pro=pro, act=ACT_SILU, bound=self._norm_bound(q + "1", spatial * (hid // 32)))
-                pro = ops.norm_finalize(self._sums(cache, x), spatial, 1, groups=32, weight=self.p[q + "4.weight"], bias=self.p[q + "4.bias"])
+                pro = self._norm(cache, [x], spatial, 1, groups=32, weight=self.p[q + "4.weight"], bias=self.p[q + "4.bias"])
                 x = self._conv(cache, [x], q + "6", cfg.cond_dim, 1, pro=pro, act=ACT_SILU, bound=self._norm_bound(q + "4", spatial * (hid // 32)))
-                pro_in = ops.norm_finalize(self._sums(cache, x), spatial, 1, groups=32, weight=self.p[q + "7.weight"], bias=self.p[q + "7.bias"])
+                pro_in = self._norm(cache, [x], spatial, 1, groups=32, weight=self.p[q + "7.weight"], bias=self.p[q + "7.bias"])
                 bound_in = self._norm_bound(q + "7", spatial * max(cfg.cond_dim // 32, 1))
         first = self.plan.input_blocks[0][0]
         return self._conv(cache, [x], first.prefix, first.cout, 3, pro=pro_in, act=act_in, bound=bound_in)
 
     def _head(self, h: torch.Tensor, cache: dict) -> torch.Tensor:
         """unet.out: LayerNorm -> LeakyReLU -> Conv3d (diffusion_network.py:869-873, :934)"""
-        pro = self.ops.norm_finalize(self._sums(cache, h), h[0].numel(), 0)
+        pro = self._norm(cache, [h], h[0].numel(), 0)
         return self._conv(cache, [h], "unet.out.2", self.cfg.out_channels, 3, pro=pro, affine_key="unet.out.0", act=ACT_LEAKY,
                           bound=self._norm_bound("unet.out.0", h[0].numel()))
 

@@ -513,6 +513,13 @@ int pixie_conv_kernel_variant(const pixie_conv_desc* desc, int* slices);
  * launch of the same tiled body.  Returns 1 for descriptors that take neither (the first-generation exact kernel).  For tests that
  * must know which kernel variant and tile geometry a shape exercises. */
 int pixie_conv_tile_geometry(const pixie_conv_desc* desc, int32_t out[10]);
+/* Where this descriptor's launch leaves the partial statistics of desc->d_out_stats, from the code pixie_stats_finalize and
+ * pixie_stats_norm_finalize read them with (a pure host function of the descriptor): out = n (partials per channel), cstride,
+ * tstride (partial t of channel c is the (sum, sum of squares) pair number c * cstride + t * tstride), f64 (1: float64 pairs, one
+ * per segment of the split-K reduce, [c_out][n][2]; 0: float32 pairs, one per tile of the conv epilogue, [n][c_out padded][2]),
+ * segment (voxels of one channel per reduce segment, the last one may be shorter; 0 for tile partials), c_out padded.
+ * Returns 1 for descriptors off the f16x3 path.  For tests that must know which statistics code a shape exercises. */
+int pixie_conv_stats_layout(const pixie_conv_desc* desc, int64_t out[6]);
 #endif /* PIXIE_DIAG */
 
 #ifdef __cplusplus

@@ -170,6 +170,7 @@ DIAG_SIGNATURES = {
     "pixie_mpm_kernel_times": (_I, [_VP, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     "pixie_conv_kernel_variant": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),
     "pixie_conv_tile_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
+    "pixie_conv_stats_layout": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int64)]),
 }
 
 _libs = {}

@@ -1279,6 +1279,17 @@ extern "C" int pixie_conv_tile_geometry(const pixie_conv_desc* d, int32_t out[10
     for (int i = 0; i < 10; ++i) out[i] = v[i];
     return 0;
 }
+
+// where this descriptor's launch leaves its partial statistics, as pixie_stats_finalize / pixie_stats_norm_finalize will read them
+// (conv16_stat_parts): out = partials per channel, cstride, tstride (in (sum, sum of squares) pairs), 1 = fp64 reduce segments /
+// 0 = fp32 tile partials, voxels per reduce segment (0 for tile partials), c_out padded.  Returns 1 off the f16x3 path.
+extern "C" int pixie_conv_stats_layout(const pixie_conv_desc* d, int64_t out[6]) {
+    if (!out || pixie_conv_stats_floats(d) <= 0) return 1;
+    const StatParts p = conv16_stat_parts(d, nullptr);
+    out[0] = p.n; out[1] = p.cstride; out[2] = p.tstride; out[3] = p.f64; out[4] = p.f64 ? kReduceSeg : 0;
+    out[5] = pixie_conv_cout_padded(d->c_out);
+    return 0;
+}
 #endif
 
 extern "C" int pixie_conv_skip_foldable(const pixie_conv_desc* d) {

@@ -41,7 +41,8 @@ def test_library_exports_every_declared_symbol():
     assert exported(_lib.LIB_PATH) == set(names), exported(_lib.LIB_PATH) ^ set(names)
     assert lib.pixie_build_arch() == b"gfx950"
     diag_names = header_symbols(diag=True)
-    assert set(diag_names) - set(names) == set(_lib.DIAG_SIGNATURES) == {"pixie_mpm_phase", "pixie_mpm_kernel_times", "pixie_conv_kernel_variant", "pixie_conv_tile_geometry"}
+    assert set(diag_names) - set(names) == set(_lib.DIAG_SIGNATURES) == {"pixie_mpm_phase", "pixie_mpm_kernel_times", "pixie_conv_kernel_variant", "pixie_conv_tile_geometry",
+                                                                                      "pixie_conv_stats_layout"}
     dlib = _lib.load(diag=True)
     assert exported(_lib.DIAG_LIB_PATH) == set(diag_names), exported(_lib.DIAG_LIB_PATH) ^ set(diag_names)
     assert dlib.pixie_build_arch() == b"gfx950"

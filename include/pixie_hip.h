@@ -487,6 +487,49 @@ int pixie_particle_volume(const float* d_pos, int n, int grid_n, double grid_dx,
 int pixie_nearest_particle(const float* d_pos, int n, const float* d_new_pos, int n_new, int32_t* d_nearest, void* stream);
 
 /* ======================================================================================
+ * (D) Forward 3D Gaussian splatting rasteriser -- the per-frame render of PG/gs_simulation.py:610-619
+ *     (diff_gaussian_rasterization.GaussianRasterizer, forward only) and PG/utils/render_utils.py:113-130 (convert_SH).
+ * ====================================================================================== */
+/* One render.  viewmatrix / projmatrix are the 16 floats of the reference's world_view_transform / full_proj_transform tensors in
+ * memory order (row-vector convention: p_view = [p, 1] . V).  The covariance is either d_cov3d ([n][6] upper triangle) or is built
+ * from scale_modifier * d_scales ([n][3]) and d_rotations ([n][4], wxyz, used un-normalised); exactly one of the two forms.
+ * d_colors is [n][3], d_opacity [n].  Outputs: d_out_color [3][height][width], d_radii [n] (0 = culled); d_final_T
+ * [height][width] (transmittance left) and d_n_contrib [height][width] (position in the pixel's tile list of the last Gaussian
+ * that contributed) where not NULL.  d_workspace: 16-byte aligned device memory of workspace_bytes bytes. */
+typedef struct pixie_raster_desc {
+    int32_t n, width, height;
+    float tanfovx, tanfovy, scale_modifier;
+    float viewmatrix[16], projmatrix[16], bg[3];
+    int32_t pad_;
+    const float* d_means;              /* [n][3] */
+    const float* d_cov3d;              /* [n][6] or NULL */
+    const float* d_scales;             /* [n][3] or NULL */
+    const float* d_rotations;          /* [n][4] or NULL */
+    const float* d_colors;             /* [n][3] */
+    const float* d_opacity;            /* [n] */
+    float* d_out_color;
+    int32_t* d_radii;
+    float* d_final_T;                  /* or NULL */
+    int32_t* d_n_contrib;              /* or NULL */
+    void* d_workspace;
+    int64_t workspace_bytes;
+} pixie_raster_desc;
+/* Bytes of workspace a render of n Gaussians at width x height needs when the Gaussians touch max_instances tiles in total
+ * (an instance = one Gaussian in one 16x16 tile).  -1 on error. */
+int64_t pixie_raster_workspace_bytes(int n, int width, int height, int64_t max_instances);
+/* Projects every Gaussian and counts the instances, synchronises `stream` ONCE to read that count (*instances_out, where not
+ * NULL), then -- asynchronously -- duplicates, sorts by (tile, depth; equal keys keep index order, so the image is reproducible bit
+ * for bit), and blends every pixel front to back: alpha = min(0.99, opacity exp(power)), skipped below 1/255, the pixel stops
+ * when T (1 - alpha) < 1e-4, out = C + T bg.  A workspace that is too small for the count returns non-zero before anything is
+ * rendered: d_radii is written, the image outputs are untouched, and pixie_last_error() and *instances_out give the count needed.
+ * n == 0 or zero instances: the background. */
+int pixie_raster_forward(const pixie_raster_desc* desc, int64_t* instances_out, void* stream);
+/* convert_SH: d_out[i] = max(SH_degree(d_shs[i]; dir_i) + 0.5, 0) with dir_i = normalise(d_pos[i] - campos), for i < n_rot first
+ * rotated by the row-major 3x3 d_rot[i].  d_shs is [n][k_coeffs][3], k_coeffs >= (degree + 1)^2, degree 0..3.  One launch. */
+int pixie_sh_to_rgb(const float* d_shs, int64_t n, int k_coeffs, int degree, const float* d_pos /* [n][3] */, const float campos[3],
+                    const float* d_rot /* [n_rot][9] or NULL */, int64_t n_rot, float* d_out /* [n][3] */, void* stream);
+
+/* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)
  * load; the production library libpixie_hip.so exports none of them and carries no trace buffer.

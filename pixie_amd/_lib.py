@@ -89,6 +89,17 @@ class FieldDesc(C.Structure):
                 ("nu_min", C.c_double), ("nu_max", C.c_double)]
 
 
+class RasterDesc(C.Structure):
+    """struct pixie_raster_desc"""
+    _fields_ = [("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
+                ("viewmatrix", C.c_float * 16), ("projmatrix", C.c_float * 16), ("bg", C.c_float * 3), ("pad_", C.c_int32),
+                ("d_means", C.c_void_p), ("d_cov3d", C.c_void_p), ("d_scales", C.c_void_p), ("d_rotations", C.c_void_p),
+                ("d_colors", C.c_void_p), ("d_opacity", C.c_void_p),
+                ("d_out_color", C.c_void_p), ("d_radii", C.c_void_p), ("d_final_T", C.c_void_p), ("d_n_contrib", C.c_void_p),
+                ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/pixie_hip.h declares: name -> (restype, argtypes)
 _VP, _I, _I64, _D, _S = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_char_p
 _D3 = C.POINTER(C.c_double)
@@ -161,6 +172,9 @@ SIGNATURES = {
     "pixie_particle_volume": (_I, [_VP, _I, _I, _D, _VP, _VP, _VP]),
     "pixie_nearest_particle": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
     "pixie_dbscan_roots": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, C.POINTER(_D), _D, _D, _I, _VP, _VP, _VP, _VP]),
+    "pixie_raster_workspace_bytes": (_I64, [_I, _I, _I, _I64]),
+    "pixie_raster_forward": (_I, [C.POINTER(RasterDesc), C.POINTER(_I64), _VP]),
+    "pixie_sh_to_rgb": (_I, [_VP, _I64, _I, _I, _VP, C.POINTER(C.c_float), _VP, _I64, _VP, _VP]),
     "pixie_field_to_particles": (_I, [C.POINTER(FieldDesc), _VP, _I, _I, _D, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 

@@ -1,0 +1,322 @@
+// pixie_amd/csrc/raster.hip -- forward 3D Gaussian splatting rasteriser: the per-frame render of PG's frame loop
+// (gs_simulation.py:610-619), and the device form of convert_SH (utils/render_utils.py:113-130).  Inference only.
+//
+// One pixie_raster_forward call is the chain
+//   raster_preprocess_kernel   one lane per Gaussian: raster_math.h project() -> depth, centre, (conic, opacity), radius, tiles touched
+//   hipcub ExclusiveSum        over n + 1 tile counts (the last is 0), so its last element is the instance count
+//   [one stream synchronise: the host reads the instance count and checks that the workspace holds it]
+//   raster_duplicate_kernel    per Gaussian, one (tile << 32 | depth bits, index) pair per tile of its rectangle
+//   hipcub SortPairs           over 32 + ceil(log2(tiles)) bits; stable, so equal (tile, depth) keep index order
+//   raster_ranges_kernel       one lane per instance: where each tile's run starts and ends
+//   raster_render_kernel       one 256-thread workgroup per 16x16 tile
+// The render kernel stages 256 instances at a time in LDS -- centre, conic + opacity and the colour (9 KiB) -- and every lane walks
+// them front to back for its pixel.  Every LDS read in that walk has one address for the whole wave (a broadcast), so what bounds
+// it is the wave's own instruction issue: per sample a ds_read_b64 and a ds_read_b128, ~28 VALU instructions up to the
+// contribution branch (expf's range handling included) and, inside that branch, a ds_read_b96 for the colour.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <climits>
+#include <cstdint>
+
+#include "../../include/pixie_hip.h"
+#include "common.h"
+#include "raster_math.h"
+
+using namespace pixie;
+namespace rm = pixie::raster;
+
+namespace {
+
+constexpr int kBlock = 256;               // = kTile * kTile: one lane per pixel of a tile
+
+__global__ void __launch_bounds__(kBlock)
+raster_preprocess_kernel(int n, rm::Camera cam, const float* __restrict__ means, const float* __restrict__ cov3d,
+                         const float* __restrict__ scales, const float* __restrict__ rotations, float scale_modifier,
+                         const float* __restrict__ opacity, float* __restrict__ depth, float2* __restrict__ centre,
+                         float4* __restrict__ conic_opacity, int32_t* __restrict__ radii, uint64_t* __restrict__ tiles_touched) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { tiles_touched[n] = 0; return; }    // the scan runs over n + 1 counts
+    float p[3], c6[6];
+    for (int d = 0; d < 3; ++d) p[d] = means[(size_t)i * 3 + d];
+    if (cov3d) {
+        for (int d = 0; d < 6; ++d) c6[d] = cov3d[(size_t)i * 6 + d];
+    } else {
+        float s[3], q[4];
+        for (int d = 0; d < 3; ++d) s[d] = scales[(size_t)i * 3 + d];
+        for (int d = 0; d < 4; ++d) q[d] = rotations[(size_t)i * 4 + d];
+        rm::cov3d_from_scale_rot(s, scale_modifier, q, c6);
+    }
+    rm::Splat2D o;
+    if (!rm::project(p, c6, cam, o)) {
+        radii[i] = 0;
+        tiles_touched[i] = 0;
+        return;
+    }
+    depth[i] = o.depth;
+    centre[i] = make_float2(o.px, o.py);
+    conic_opacity[i] = make_float4(o.ca, o.cb, o.cc, opacity[i]);
+    radii[i] = o.radius;
+    tiles_touched[i] = (uint64_t)((o.x1 - o.x0) * (o.y1 - o.y0));
+}
+
+__global__ void __launch_bounds__(kBlock)
+raster_duplicate_kernel(int n, int tiles_x, int tiles_y, const float2* __restrict__ centre, const float* __restrict__ depth,
+                        const int32_t* __restrict__ radii, const uint64_t* __restrict__ offsets, uint64_t* __restrict__ keys,
+                        uint32_t* __restrict__ values) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int r = radii[i];
+    if (r <= 0) return;
+    const float2 c = centre[i];
+    int x0, y0, x1, y1;
+    rm::tile_rect(c.x, c.y, r, tiles_x, tiles_y, x0, y0, x1, y1);
+    uint64_t off = offsets[i];
+    const uint64_t end = offsets[i + 1];             // never written past: the rectangle is the one preprocess counted
+    const uint64_t dbits = (uint64_t)__float_as_uint(depth[i]);
+    for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x) {
+            if (off >= end) return;
+            keys[off] = ((uint64_t)(uint32_t)(y * tiles_x + x) << 32) | dbits;
+            values[off] = (uint32_t)i;
+            ++off;
+        }
+}
+
+__global__ void __launch_bounds__(kBlock)
+raster_ranges_kernel(int64_t count, const uint64_t* __restrict__ keys, uint2* __restrict__ ranges) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t tile = (uint32_t)(keys[i] >> 32);
+    if (i == 0) {
+        ranges[tile].x = 0u;
+    } else {
+        const uint32_t prev = (uint32_t)(keys[i - 1] >> 32);
+        if (prev != tile) {
+            ranges[prev].y = (uint32_t)i;
+            ranges[tile].x = (uint32_t)i;
+        }
+    }
+    if (i == count - 1) ranges[tile].y = (uint32_t)count;
+}
+
+__global__ void __launch_bounds__(kBlock)
+raster_render_kernel(int W, int H, int tiles_x, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+                     const float2* __restrict__ centre, const float4* __restrict__ conic_opacity, const float* __restrict__ colors,
+                     float bg0, float bg1, float bg2, float* __restrict__ out_color, float* __restrict__ final_T,
+                     int32_t* __restrict__ n_contrib) {
+    __shared__ float2 s_xy[kBlock];
+    __shared__ float4 s_co[kBlock];
+    __shared__ float3 s_rgb[kBlock];
+    const int tid = threadIdx.x;                     // wave w owns rows 4w .. 4w+3 of the tile
+    const int pix_x = blockIdx.x * rm::kTile + (tid & (rm::kTile - 1));
+    const int pix_y = blockIdx.y * rm::kTile + (tid >> 4);
+    const bool inside = pix_x < W && pix_y < H;
+    const float fx = (float)pix_x, fy = (float)pix_y;
+    const uint2 range = ranges[blockIdx.y * tiles_x + blockIdx.x];
+    int todo = (int)(range.y - range.x);
+    rm::PixelAcc acc = rm::pixel_start(!inside);
+
+    for (uint32_t base = range.x; base < range.y; base += kBlock, todo -= kBlock) {
+        if (__syncthreads_count(acc.done) == kBlock) break;      // also the barrier that frees the staging buffers
+        if (base + tid < range.y) {
+            const uint32_t g = point_list[base + tid];
+            s_xy[tid] = centre[g];
+            s_co[tid] = conic_opacity[g];
+            s_rgb[tid] = make_float3(colors[(size_t)g * 3], colors[(size_t)g * 3 + 1], colors[(size_t)g * 3 + 2]);
+        }
+        __syncthreads();
+        const int cnt = todo < kBlock ? todo : kBlock;
+        for (int j = 0; !acc.done && j < cnt; ++j) {
+            const float2 xy = s_xy[j];
+            const float4 co = s_co[j];
+            const float3 rgb = s_rgb[j];
+            rm::blend(acc, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, fx, fy);
+        }
+    }
+    if (inside) {
+        const size_t pix = (size_t)pix_y * W + pix_x;
+        const size_t plane = (size_t)W * H;
+        out_color[pix] = acc.r + acc.T * bg0;
+        out_color[plane + pix] = acc.g + acc.T * bg1;
+        out_color[2 * plane + pix] = acc.b + acc.T * bg2;
+        if (final_T) final_T[pix] = acc.T;
+        if (n_contrib) n_contrib[pix] = (int32_t)acc.last;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+sh_to_rgb_kernel(const float* __restrict__ shs, int64_t n, int k_coeffs, int degree, const float* __restrict__ pos, float cx, float cy,
+                 float cz, const float* __restrict__ rot, int64_t n_rot, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float dx = pos[i * 3] - cx, dy = pos[i * 3 + 1] - cy, dz = pos[i * 3 + 2] - cz;
+    if (i < n_rot) {
+        const float* R = rot + i * 9;
+        const float rx = R[0] * dx + R[1] * dy + R[2] * dz;
+        const float ry = R[3] * dx + R[4] * dy + R[5] * dz;
+        const float rz = R[6] * dx + R[7] * dy + R[8] * dz;
+        dx = rx; dy = ry; dz = rz;
+    }
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    float rgb[3];
+    rm::sh_to_rgb(shs + i * k_coeffs * 3, degree, dx / len, dy / len, dz / len, rgb);
+    for (int d = 0; d < 3; ++d) out[i * 3 + d] = rgb[d];
+}
+
+// Workspace: the part steps 1-2 need, whose size depends on (n, tiles) only, then the part sized by the instance count.
+struct Layout {
+    size_t depth, centre, conic_opacity, tiles_touched, offsets, ranges, scan_temp, scan_temp_bytes, fixed_bytes;
+    size_t keys_in, keys_out, vals_in, vals_out, sort_temp, sort_temp_bytes, total_bytes;
+};
+
+size_t take(size_t& cursor, size_t bytes) {
+    const size_t at = cursor;
+    cursor = (cursor + bytes + 255) & ~(size_t)255;
+    return at;
+}
+
+int sort_end_bit(int tiles) {
+    int bits = 0;
+    while ((1LL << bits) < tiles) ++bits;
+    return 32 + bits;
+}
+
+int make_layout(int n, int tiles, int64_t instances, Layout& L) {
+    size_t cur = 0;
+    L.depth = take(cur, sizeof(float) * (size_t)n);
+    L.centre = take(cur, sizeof(float2) * (size_t)n);
+    L.conic_opacity = take(cur, sizeof(float4) * (size_t)n);
+    L.tiles_touched = take(cur, sizeof(uint64_t) * ((size_t)n + 1));
+    L.offsets = take(cur, sizeof(uint64_t) * ((size_t)n + 1));
+    L.ranges = take(cur, sizeof(uint2) * (size_t)tiles);
+    L.scan_temp_bytes = 0;
+    PX_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, L.scan_temp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, n + 1));
+    L.scan_temp = take(cur, L.scan_temp_bytes);
+    L.fixed_bytes = cur;
+    const size_t m = (size_t)instances;
+    L.keys_in = take(cur, sizeof(uint64_t) * m);
+    L.keys_out = take(cur, sizeof(uint64_t) * m);
+    L.vals_in = take(cur, sizeof(uint32_t) * m);
+    L.vals_out = take(cur, sizeof(uint32_t) * m);
+    L.sort_temp_bytes = 0;
+    if (m > 0)
+        PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, L.sort_temp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, m, 0, sort_end_bit(tiles)));
+    L.sort_temp = take(cur, L.sort_temp_bytes);
+    L.total_bytes = cur;
+    return 0;
+}
+
+int check_shape(const char* who, int n, int width, int height) {
+    PX_REQUIRE(n >= 0, "%s: n %d < 0", who, n);
+    PX_REQUIRE(n < INT_MAX, "%s: n %d exceeds one scan (n + 1 counts)", who, n);
+    PX_REQUIRE(width > 0 && height > 0, "%s: image %d x %d must be positive", who, width, height);
+    PX_REQUIRE(width <= 65536 && height <= 65536, "%s: image %d x %d exceeds 65536 per side", who, width, height);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pixie_raster_workspace_bytes(int n, int width, int height, int64_t max_instances) {
+    if (check_shape("pixie_raster_workspace_bytes", n, width, height)) return -1;
+    if (max_instances < 0 || max_instances > (int64_t)UINT32_MAX) {
+        set_error("pixie_raster_workspace_bytes: max_instances %lld outside [0, 2^32)", (long long)max_instances);
+        return -1;
+    }
+    const int tiles = cdiv(width, rm::kTile) * cdiv(height, rm::kTile);
+    Layout L;
+    if (make_layout(n, tiles, max_instances, L)) return -1;
+    return (int64_t)L.total_bytes;
+}
+
+int pixie_raster_forward(const pixie_raster_desc* d, int64_t* instances_out, void* stream) {
+    PX_REQUIRE(d, "pixie_raster_forward: null descriptor");
+    if (instances_out) *instances_out = 0;
+    if (check_shape("pixie_raster_forward", d->n, d->width, d->height)) return 1;
+    PX_REQUIRE(d->tanfovx > 0.0f && d->tanfovy > 0.0f, "pixie_raster_forward: tanfovx %g, tanfovy %g must be positive", d->tanfovx, d->tanfovy);
+    PX_REQUIRE(d->d_out_color, "pixie_raster_forward: null pointer (d_out_color is required)");
+    const int n = d->n;
+    if (n > 0) {
+        PX_REQUIRE(d->d_means && d->d_colors && d->d_opacity && d->d_radii,
+                   "pixie_raster_forward: null pointer (d_means, d_colors, d_opacity and d_radii are required)");
+        PX_REQUIRE((d->d_cov3d != nullptr) != (d->d_scales != nullptr || d->d_rotations != nullptr),
+                   "pixie_raster_forward: give either d_cov3d or the pair d_scales, d_rotations");
+        PX_REQUIRE(d->d_cov3d || (d->d_scales && d->d_rotations), "pixie_raster_forward: d_scales and d_rotations go together");
+    }
+    const rm::Camera cam = rm::make_camera(d->viewmatrix, d->projmatrix, d->tanfovx, d->tanfovy, d->width, d->height);
+    const int tiles = cam.tiles_x * cam.tiles_y;
+    Layout L;
+    if (make_layout(n, tiles, 0, L)) return 1;
+    PX_REQUIRE(d->d_workspace && d->workspace_bytes >= (int64_t)L.fixed_bytes,
+               "pixie_raster_forward: workspace of %lld bytes is smaller than the %lld bytes that %d Gaussians and %d tiles need before any instance",
+               (long long)d->workspace_bytes, (long long)L.fixed_bytes, n, tiles);
+    PX_REQUIRE(((uintptr_t)d->d_workspace & 15) == 0, "pixie_raster_forward: d_workspace must be 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    char* ws = (char*)d->d_workspace;
+    float* depth = (float*)(ws + L.depth);
+    float2* centre = (float2*)(ws + L.centre);
+    float4* conic_opacity = (float4*)(ws + L.conic_opacity);
+    uint64_t* tiles_touched = (uint64_t*)(ws + L.tiles_touched);
+    uint64_t* offsets = (uint64_t*)(ws + L.offsets);
+    uint2* ranges = (uint2*)(ws + L.ranges);
+
+    uint64_t count = 0;
+    if (n > 0) {
+        hipLaunchKernelGGL(raster_preprocess_kernel, dim3(cdiv((long)n + 1, kBlock)), dim3(kBlock), 0, st, n, cam, d->d_means, d->d_cov3d,
+                           d->d_scales, d->d_rotations, d->scale_modifier, d->d_opacity, depth, centre, conic_opacity, d->d_radii, tiles_touched);
+        PX_CHECK_HIP(hipGetLastError());
+        size_t tb = L.scan_temp_bytes;
+        PX_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_temp, tb, (const uint64_t*)tiles_touched, offsets, n + 1, st));
+        PX_CHECK_HIP(hipMemcpyAsync(&count, offsets + n, sizeof count, hipMemcpyDeviceToHost, st));
+        PX_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    if (instances_out) *instances_out = (int64_t)count;
+    PX_REQUIRE(count <= (uint64_t)UINT32_MAX, "pixie_raster_forward: %llu instances exceed 2^32", (unsigned long long)count);
+    if (make_layout(n, tiles, (int64_t)count, L)) return 1;
+    PX_REQUIRE((int64_t)L.total_bytes <= d->workspace_bytes,
+               "pixie_raster_forward: workspace too small: %llu instances need %lld bytes, the workspace has %lld",
+               (unsigned long long)count, (long long)L.total_bytes, (long long)d->workspace_bytes);
+
+    PX_CHECK_HIP(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)tiles, st));
+    uint32_t* sorted_vals = (uint32_t*)(ws + L.vals_out);
+    if (count > 0) {
+        uint64_t* keys_in = (uint64_t*)(ws + L.keys_in);
+        uint64_t* keys_out = (uint64_t*)(ws + L.keys_out);
+        uint32_t* vals_in = (uint32_t*)(ws + L.vals_in);
+        hipLaunchKernelGGL(raster_duplicate_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st, n, cam.tiles_x, cam.tiles_y, centre, depth,
+                           d->d_radii, offsets, keys_in, vals_in);
+        PX_CHECK_HIP(hipGetLastError());
+        size_t tb = L.sort_temp_bytes;
+        PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.sort_temp, tb, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
+                                                        sorted_vals, (size_t)count, 0, sort_end_bit(tiles), st));
+        hipLaunchKernelGGL(raster_ranges_kernel, dim3(cdiv((long)count, kBlock)), dim3(kBlock), 0, st, (int64_t)count, keys_out, ranges);
+        PX_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(raster_render_kernel, dim3(cam.tiles_x, cam.tiles_y), dim3(kBlock), 0, st, d->width, d->height, cam.tiles_x, ranges,
+                       sorted_vals, centre, conic_opacity, d->d_colors, d->bg[0], d->bg[1], d->bg[2], d->d_out_color, d->d_final_T,
+                       d->d_n_contrib);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int pixie_sh_to_rgb(const float* d_shs, int64_t n, int k_coeffs, int degree, const float* d_pos, const float campos[3], const float* d_rot,
+                    int64_t n_rot, float* d_out, void* stream) {
+    PX_REQUIRE(n >= 0, "pixie_sh_to_rgb: n %lld < 0", (long long)n);
+    PX_REQUIRE(degree >= 0 && degree <= 3, "pixie_sh_to_rgb: degree %d outside 0..3", degree);
+    PX_REQUIRE(k_coeffs >= (degree + 1) * (degree + 1), "pixie_sh_to_rgb: %d coefficients are fewer than degree %d needs", k_coeffs, degree);
+    PX_REQUIRE(n_rot >= 0 && n_rot <= n, "pixie_sh_to_rgb: n_rot %lld outside [0, n]", (long long)n_rot);
+    if (n == 0) return 0;
+    PX_REQUIRE(d_shs && d_pos && campos && d_out, "pixie_sh_to_rgb: null pointer (d_shs, d_pos, campos and d_out are required)");
+    PX_REQUIRE(n_rot == 0 || d_rot, "pixie_sh_to_rgb: n_rot %lld without d_rot", (long long)n_rot);
+    PX_REQUIRE(n <= (int64_t)INT_MAX * kBlock / 2, "pixie_sh_to_rgb: n %lld exceeds one launch", (long long)n);
+    hipLaunchKernelGGL(sh_to_rgb_kernel, dim3((unsigned)cdiv(n, kBlock)), dim3(kBlock), 0, as_stream(stream), d_shs, n, k_coeffs, degree, d_pos,
+                       campos[0], campos[1], campos[2], d_rot, n_rot, d_out);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

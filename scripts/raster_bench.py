@@ -1,0 +1,71 @@
+#!/usr/bin/env python
+"""Times the forward rasteriser at the frame-export sizes of DESIGN 3.8: a ball of N Gaussians (the synthetic MPM scene's sizes) at
+800 x 800.  HIP events around whole GaussianRasterizer calls (which include the one stream synchronise that reads the instance
+count); per-launch times come from running this script under `rocprofv3 --kernel-trace --stats`.  Prints one line per size."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pixie_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer  # noqa: E402
+
+
+def look_at_camera(eye, target, fovx_deg, W, H, up, znear=0.01, zfar=100.0):
+    """row-vector view and full projection matrices of a pinhole camera (+z forward, y down), tan of the half fields of view"""
+    eye, target, up = (np.asarray(v, np.float64) for v in (eye, target, up))
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, up)
+    right /= np.linalg.norm(right)
+    V = np.eye(4)
+    V[:3, :3] = np.stack([right, np.cross(fwd, right), fwd], axis=1)
+    V[3, :3] = -eye @ V[:3, :3]
+    tanx = np.tan(np.radians(fovx_deg) / 2.0)
+    tany = tanx * H / W
+    Pm = np.zeros((4, 4))
+    Pm[0, 0], Pm[1, 1], Pm[2, 2], Pm[3, 2], Pm[2, 3] = 1.0 / tanx, 1.0 / tany, zfar / (zfar - znear), -(zfar * znear) / (zfar - znear), 1.0
+    return dict(V=V.astype(np.float32), P=(V @ Pm).astype(np.float32), tanfovx=float(tanx), tanfovy=float(tany), campos=eye.astype(np.float32))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[100_000, 350_000])
+    ap.add_argument("--size", type=int, default=800)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    for n in a.n:
+        rng = np.random.default_rng(0)
+        d = rng.normal(size=(n, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        pos = (d * (0.5 * rng.random(n) ** (1 / 3))[:, None]).astype(np.float32)
+        s2 = rng.uniform(1e-5, 4e-5, n).astype(np.float32)
+        cov = np.zeros((n, 6), np.float32)
+        cov[:, 0] = cov[:, 3] = cov[:, 5] = s2
+        cam = look_at_camera((0.0, -2.4, 0.3), (0.0, 0.0, 0.0), 40.0, a.size, a.size, up=(0.0, 0.0, -1.0))
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        st = GaussianRasterizationSettings(a.size, a.size, cam["tanfovx"], cam["tanfovy"], t(np.ones(3, np.float32)), 1.0, t(cam["V"]), t(cam["P"]), 0,
+                                           t(cam["campos"]), False, False)
+        r = GaussianRasterizer(st)
+        args = (t(pos), None, t(rng.uniform(0.2, 1.0, n).astype(np.float32)))
+        kw = dict(colors_precomp=t(rng.uniform(0, 1, (n, 3)).astype(np.float32)), cov3D_precomp=t(cov))
+        for _ in range(a.warmup):
+            img, radii, fT, nc = r(*args, aux=True, **kw)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            r(*args, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        print(json.dumps(dict(n=n, width=a.size, height=a.size, instances=r.last_instances, visible=int((radii > 0).sum()),
+                              call_ms=e0.elapsed_time(e1) / a.reps, reps=a.reps, mean_n_contrib=float(nc.float().mean()),
+                              max_n_contrib=int(nc.max()), saturated_pixel_share=float((fT < 1e-2).float().mean()))), flush=True)
+
+
+if __name__ == "__main__":
+    main()

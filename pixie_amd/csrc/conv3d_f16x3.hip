@@ -33,6 +33,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "conv_plan.h"
 
 namespace pixie {
 
@@ -956,294 +957,250 @@ __global__ void pack_weights_subpixel_kernel(const float* __restrict__ src, uint
     dst[kW16HeaderU4 + total + i] = __builtin_bit_cast(uint4, vl);
 }
 
-static unsigned magic_of16(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
-static int ilog2_16(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-static int pow2_le16(int v, int cap) { int p = 1; while (p * 2 <= v && p * 2 <= cap) p *= 2; return p; }
+// split-K launches: segments per channel of splitk_reduce_stats_kernel = partial statistics per channel
+static int reduce_segments(long osp) { return (int)((osp + kReduceSeg - 1) / kReduceSeg); }
 
-template <int MB>
-static int launch_subpixel(const Conv16Args& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
-    auto kern = conv3d_f16x3_subpixel_kernel<MB>;
-    PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
-    PX_CHECK_HIP(hipGetLastError());
-    return 0;
+bool conv_exact_v1() { return getenv("PIXIE_CONV_EXACT_V1") != nullptr; }
+
+ConvShape conv_shape_of(const pixie_conv_desc* d) {
+    ConvShape s;
+    s.c0 = d->c0; s.c1 = d->c1; s.c_out = d->c_out;
+    s.in_d = d->in_d; s.in_h = d->in_h; s.in_w = d->in_w;
+    s.ksize = d->ksize; s.stride = d->stride; s.upsample = d->upsample;
+    s.out_d = d->out_d; s.out_h = d->out_h; s.out_w = d->out_w;
+    s.skip_c0 = d->skip_c0; s.skip_c1 = d->skip_c1;
+    s.w16 = d->d_w16 != nullptr; s.subpixel = d->w16_subpixel != 0; s.workspace = d->d_workspace != nullptr; s.skip = d->d_skip_w16 != nullptr;
+    s.exact_v1 = conv_exact_v1();
+    return s;
 }
 
-// does this descriptor take the sub-pixel path (w16_subpixel says how d_w16 was packed; the shape must allow it)
-static bool conv16_subpixel(const pixie_conv_desc* d) {
-    return d->d_w16 && d->w16_subpixel && d->upsample == 1 && d->ksize == 3 && d->stride == 1;
+// the output dims of a convolution: padding ksize / 2, nearest x2 upsampling first, cropped to out_* where given
+static void conv_output_dims(const ConvShape& s, int& od, int& oh, int& ow) {
+    const int pad = s.ksize == 3 ? 1 : 0;
+    od = ((s.in_d << s.upsample) + 2 * pad - s.ksize) / s.stride + 1;
+    oh = ((s.in_h << s.upsample) + 2 * pad - s.ksize) / s.stride + 1;
+    ow = ((s.in_w << s.upsample) + 2 * pad - s.ksize) / s.stride + 1;
+    if (s.out_d > 0) od = std::min(od, s.out_d);   // odd-grid crop (diffusion_network.py:925-930)
+    if (s.out_h > 0) oh = std::min(oh, s.out_h);
+    if (s.out_w > 0) ow = std::min(ow, s.out_w);
 }
 
-template <int KS, int MB, int NB>
-static int launch_f16x3(const Conv16Args& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
-    auto kern = conv3d_f16x3_kernel<KS, MB, NB>;
-    PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
-    PX_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// geometry + tile selection shared by the launcher, pixie_conv_stats_floats and pixie_stats_finalize
-static void conv16_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, int& NB_out, int* slices_out = nullptr) {
-    a.ID = d->in_d; a.IH = d->in_h; a.IW = d->in_w;
-    a.ups = d->upsample;
-    a.LD = a.ID << a.ups; a.LH = a.IH << a.ups; a.LW = a.IW << a.ups;
-    const int pad = d->ksize == 3 ? 1 : 0;
-    a.stride = d->stride;
-    a.OD = (a.LD + 2 * pad - d->ksize) / a.stride + 1; a.OH = (a.LH + 2 * pad - d->ksize) / a.stride + 1; a.OW = (a.LW + 2 * pad - d->ksize) / a.stride + 1;
-    if (d->out_d > 0) a.OD = std::min(a.OD, (int)d->out_d);   // odd-grid crop (diffusion_network.py:925-930)
-    if (d->out_h > 0) a.OH = std::min(a.OH, (int)d->out_h);
-    if (d->out_w > 0) a.OW = std::min(a.OW, (int)d->out_w);
-    a.cout = d->c_out; a.coutp = pixie_conv_cout_padded(d->c_out);
-    const int chunks = (d->c0 + d->c1) / 16;
-    const int smax = d->d_workspace ? std::min(8, chunks / 2) : 1;
-    if (conv16_subpixel(d)) {
+// Path, kernel entry, split factor, tile and buffer sizes of one launch.  A refused plan (path CONV_NONE) says why and keeps what
+// was decided up to there (output dims, LDS request) for the caller's message; its buffer sizes are still 0.
+ConvPlan conv_plan(const ConvShape& s) {
+    ConvPlan p;
+    auto refuse = [&p](ConvRefusal why) { p.path = CONV_NONE; p.refusal = why; return p; };
+    if ((s.ksize != 1 && s.ksize != 3) || (s.stride != 1 && s.stride != 2) || (s.upsample != 0 && s.upsample != 1) || s.c0 <= 0 || s.c1 < 0 ||
+        s.c_out <= 0 || s.in_d <= 0 || s.in_h <= 0 || s.in_w <= 0)
+        return refuse(CONV_BAD_SHAPE);
+    conv_output_dims(s, p.OD, p.OH, p.OW);
+    p.KS = s.ksize; p.coutp = pixie_conv_cout_padded(s.c_out);
+    p.ups = s.upsample; p.LD = s.in_d << p.ups; p.LH = s.in_h << p.ups; p.LW = s.in_w << p.ups;
+    // which path: the tiled body takes 16-channel chunks, and stride 2 only under a 3^3 kernel without upsampling (the Downsample
+    // convs); its f16x3 form reads the first input in groups of 8 channels.  Exact-fp32 descriptors that do not fit keep the
+    // first-generation kernel of conv3d_mfma.hip (odd channel counts, tiny test networks); f16x3 ones are refused.
+    const int cin = s.c0 + s.c1;
+    const bool stride_ok = s.stride == 1 || (s.ksize == 3 && !s.upsample), chunks_ok = cin % 16 == 0;
+    if (!s.w16) {
+        if (!stride_ok || !chunks_ok || s.exact_v1) { p.path = CONV_FIRST_GEN; return p; }
+        p.path = CONV_EXACT_TILED;
+    } else {
+        if (!stride_ok) return refuse(CONV_BAD_STRIDE);
+        if (!chunks_ok || s.c0 % 8 != 0) return refuse(CONV_BAD_CHANNELS);
+        // (subpixel says how the weights were packed; the shape must allow it)
+        if (s.subpixel && !(s.upsample == 1 && s.ksize == 3 && s.stride == 1 && !s.skip)) return refuse(CONV_BAD_SUBPIXEL);
+        p.path = s.subpixel ? CONV_F16X3_SUBPIXEL : CONV_F16X3;
+    }
+    const bool sub = p.path == CONV_F16X3_SUBPIXEL;
+    const int chunks = cin / 16;
+    const int smax = (p.f16x3() && s.workspace) ? std::min(8, chunks / 2) : 1;   // no split-K on the exact path: small layers shrink the tile instead
+    // a tile of at most `vox` voxels over an extent
+    auto tile = [&p](int ED, int EH, int EW, int vox) {
+        p.TX = pow2_le(EW, 32);
+        p.TY = pow2_le(EH, std::max(1, std::min(4, vox / p.TX)));
+        p.TZ = std::max(1, std::min(ED, vox / (p.TX * p.TY)));
+        p.lTX = ilog2(p.TX); p.lTY = ilog2(p.TY);
+        p.tiles_x = (EW + p.TX - 1) / p.TX; p.tiles_y = (EH + p.TY - 1) / p.TY; p.tiles_z = (ED + p.TZ - 1) / p.TZ;
+        p.n_tiles = p.tiles_x * p.tiles_y * p.tiles_z;
+    };
+    if (sub) {
         // the tile lies over the STORED voxels that have an output: 4 waves x 64 voxels, each worth two x parities; one
         // workgroup per tile and (z, y) parity, the parity fastest: where the body's XCD remap applies and the tile count is a
         // multiple of 8 (every shape of the 128^3 network) the four parities of a tile run in one XCD and share their input in
         // its L2; otherwise they may straddle XCDs and meet in the MALL instead (performance only)
-        a.ups = 0; a.LD = a.ID; a.LH = a.IH; a.LW = a.IW;
-        const int SD = (a.OD + 1) / 2, SH = (a.OH + 1) / 2, SW = (a.OW + 1) / 2;
-        a.TX = pow2_le16(SW, 32);
-        a.TY = pow2_le16(SH, std::max(1, std::min(4, 256 / a.TX)));
-        a.TZ = std::max(1, std::min(SD, 256 / (a.TX * a.TY)));
-        a.lTX = ilog2_16(a.TX); a.lTY = ilog2_16(a.TY);
-        a.tiles_x = (SW + a.TX - 1) / a.TX; a.tiles_y = (SH + a.TY - 1) / a.TY; a.tiles_z = (SD + a.TZ - 1) / a.TZ;
-        a.n_tiles = 4 * a.tiles_x * a.tiles_y * a.tiles_z;
-        a.HX = a.TX + 2; a.HY = a.TY + 1; a.HZ = a.TZ + 1;
-        a.HYX = a.HY * a.HX; a.CS = a.HZ * a.HYX;
-        a.mHX = magic_of16(a.HX); a.mHYX = magic_of16(a.HYX);
-        MB_out = (a.coutp >= 64) ? 2 : 1; NB_out = 4;
-        int sl = 1;   // too few workgroups for the chip: split the channel chunks (needs the caller's workspace)
-        const long wgs = (long)a.n_tiles * ((a.coutp + MB_out * 32 - 1) / (MB_out * 32));
-        while (sl * 2 <= smax && wgs * sl < 512) sl *= 2;
-        if (slices_out) *slices_out = sl;
-        return;
-    }
-    const long ovol = (long)a.OD * a.OH * a.OW;
-    int MB = (a.coutp >= 64) ? 2 : 1;
-    int NB = (a.stride == 2) ? 1 : 4;   // stride 2: the tile holds 8x the voxels it produces; only NB = 1 fits (112 KB, one workgroup per CU)
-    auto n_wg = [&](int mb, int nb) {
-        const long tiles = (ovol + 128L * nb - 1) / (128L * nb);
-        return tiles * ((a.coutp + mb * 32 - 1) / (mb * 32));
-    };
-    // Split-K (needs the caller's workspace): when the output is too small to give every CU two workgroups, keep the
-    // big MFMA-efficient tile and split the channel chunks over up to 8 slices instead of shrinking the tile; the
-    // slices write partial outputs that splitk_reduce_kernel adds in a fixed order.
-    int slices = 1;
-    if (smax >= 2 && n_wg(MB, NB) < 512) {
-        bool found = false;
-        for (int nb = NB; nb >= 1 && !found; nb /= 2) {
-            for (int sl = 1; sl <= smax; sl *= 2)
-                if (n_wg(MB, nb) * sl >= 512) { NB = nb; slices = sl; found = true; break; }
-        }
-        if (!found) { NB = 1; slices = 1; while (slices * 2 <= smax) slices *= 2; }
+        p.ups = 0; p.LD = s.in_d; p.LH = s.in_h; p.LW = s.in_w;
+        tile((p.OD + 1) / 2, (p.OH + 1) / 2, (p.OW + 1) / 2, 256);
+        p.n_tiles *= 4;
+        p.HX = p.TX + 2; p.HY = p.TY + 1; p.HZ = p.TZ + 1;
+        p.MB = (p.coutp >= 64) ? 2 : 1; p.NB = 4;
+        // too few workgroups for the chip: split the channel chunks (needs the caller's workspace)
+        const long wgs = (long)p.n_tiles * ((p.coutp + p.MB * 32 - 1) / (p.MB * 32));
+        while (p.slices * 2 <= smax && wgs * p.slices < 512) p.slices *= 2;
     } else {
-        while (n_wg(MB, NB) < 512 && NB > 1) NB /= 2;
-        if (n_wg(MB, NB) < 512 && MB > 1) MB = 1;
-    }
-    if (slices_out) *slices_out = slices;
-    const int tile_vox = 128 * NB;
-    a.TX = pow2_le16(a.OW, 32);
-    a.TY = pow2_le16(a.OH, std::max(1, std::min(4, tile_vox / a.TX)));
-    a.TZ = std::max(1, std::min(a.OD, tile_vox / (a.TX * a.TY)));
-    a.lTX = ilog2_16(a.TX); a.lTY = ilog2_16(a.TY);
-    a.tiles_x = (a.OW + a.TX - 1) / a.TX; a.tiles_y = (a.OH + a.TY - 1) / a.TY; a.tiles_z = (a.OD + a.TZ - 1) / a.TZ;
-    a.n_tiles = a.tiles_x * a.tiles_y * a.tiles_z;
-    a.HX = (a.TX - 1) * a.stride + d->ksize; a.HY = (a.TY - 1) * a.stride + d->ksize; a.HZ = (a.TZ - 1) * a.stride + d->ksize;
-    a.HYX = a.HY * a.HX; a.CS = a.HZ * a.HYX;
-    a.mHX = magic_of16(a.HX); a.mHYX = magic_of16(a.HYX);
-
-    MB_out = MB; NB_out = NB;
-}
-
-// split-K launches: segments per channel of splitk_reduce_stats_kernel = partial statistics per channel
-static int reduce_segments(long osp) { return (int)((osp + kReduceSeg - 1) / kReduceSeg); }
-
-// where the launch of this descriptor leaves its partial statistics (d_out_stats): per tile in fp32, or per reduce segment in fp64
-static StatParts conv16_stat_parts(const pixie_conv_desc* d, const void* stats) {
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(d, a, MB, NB, &slices);
-    if (slices > 1) {
-        const int n = reduce_segments((long)a.OD * a.OH * a.OW);
-        return StatParts{stats, n, n, 1, 1};
-    }
-    return StatParts{stats, a.n_tiles, 1, a.coutp, 0};
-}
-
-// LDS the transposing epilogue needs (4 waves x 32 rows x (NB*32 + 4) floats + the statistics partials), and whether a launch
-// gets it: unsplit launches only, as long as two workgroups still fit on a CU.  One decision for both launchers and for
-// pixie_conv_tile_geometry.
-static size_t conv16_epi_bytes(int MB, int NB) { return ((size_t)4 * 32 * (NB * 32 + 4) + (size_t)4 * MB * 32 * 2) * sizeof(float); }
-static bool conv16_epi_lds(int MB, int NB, int slices) { return slices == 1 && conv16_epi_bytes(MB, NB) <= 80 * 1024; }
-
-// the exact-fp32 launch's tiling: conv16_tiling without a workspace (no split-K on this path: small layers shrink the tile instead)
-static void conv16_exact_tiling(const pixie_conv_desc* d, Conv16Args& a, int& MB_out, int& NB_out) {
-    pixie_conv_desc probe = *d;
-    probe.d_workspace = nullptr;
-    probe.w16_subpixel = 0;
-    int slices = 1;
-    conv16_tiling(&probe, a, MB_out, NB_out, &slices);
-}
-
-// called by pixie_conv3d_forward (conv3d_mfma.hip) when the descriptor carries f16x2-packed weights
-int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st) {
-    PX_REQUIRE(d->stride == 1 || (d->stride == 2 && d->ksize == 3 && !d->upsample), "f16x3 conv: stride must be 1, or 2 for a 3^3 kernel");
-    const int cin = d->c0 + d->c1;
-    PX_REQUIRE(cin % 16 == 0 && d->c0 % 8 == 0, "f16x3 conv: c_in must be a multiple of 16 (got %d+%d)", d->c0, d->c1);
-    PX_REQUIRE(d->d_in_amax0 != nullptr || d->in_bound > 0.0f, "f16x3 conv: needs d_in_amax0 or a positive in_bound");
-    PX_REQUIRE(d->c1 == 0 || d->d_in_amax0 == nullptr || d->d_in_amax1 != nullptr, "f16x3 conv: second input needs its own amax slot");
-    Conv16Args a{};
-    a.in0 = d->d_in0; a.in1 = d->d_in1; a.c0 = d->c0; a.cin = cin;
-    a.ID = d->in_d; a.IH = d->in_h; a.IW = d->in_w;
-    a.ups = d->upsample;
-    a.LD = a.ID << a.ups; a.LH = a.IH << a.ups; a.LW = a.IW << a.ups;
-    const int pad = d->ksize == 3 ? 1 : 0;
-    a.stride = d->stride;
-    a.OD = (a.LD + 2 * pad - d->ksize) / a.stride + 1; a.OH = (a.LH + 2 * pad - d->ksize) / a.stride + 1; a.OW = (a.LW + 2 * pad - d->ksize) / a.stride + 1;
-    if (d->out_d > 0) a.OD = std::min(a.OD, (int)d->out_d);   // odd-grid crop (diffusion_network.py:925-930)
-    if (d->out_h > 0) a.OH = std::min(a.OH, (int)d->out_h);
-    if (d->out_w > 0) a.OW = std::min(a.OW, (int)d->out_w);
-    a.pro_a = d->d_pro_a; a.pro_b = d->d_pro_b; a.gamma = d->d_gamma; a.beta = d->d_beta; a.act = d->act;
-    a.w16 = reinterpret_cast<const uint4*>(d->d_w16); a.bias = d->d_bias; a.cout = d->c_out; a.coutp = pixie_conv_cout_padded(d->c_out);
-    a.residual = d->d_residual; a.out = d->d_out;
-    a.amax0 = d->d_in_amax0; a.amax1 = (d->c1 > 0) ? d->d_in_amax1 : nullptr; a.in_bound = d->in_bound;
-    a.stats = d->d_out_stats; a.out_amax = d->d_out_amax;
-
-    int MB = 0, NB = 0, slices = 1;
-    const bool sp = d->w16_subpixel != 0;
-    PX_REQUIRE(!sp || (conv16_subpixel(d) && !d->d_skip_w16), "f16x3 conv: sub-pixel weights need upsample = 1, ksize = 3, stride = 1 and no folded skip");
-    conv16_tiling(d, a, MB, NB, &slices);   // (sub-pixel: a.ups, a.L* now describe the stored tensor)
-    if (d->d_skip_w16) {
-        const int scin = d->skip_c0 + d->skip_c1;
-        PX_REQUIRE(pixie_conv_skip_foldable(d), "f16x3 conv: this launch cannot fold a skip convolution (pixie_conv_skip_foldable)");
-        PX_REQUIRE(d->d_skip_in0 && d->d_skip_amax0 && (d->skip_c1 == 0 || (d->d_skip_in1 && d->d_skip_amax1)), "f16x3 conv: folded skip needs its inputs and their amax slots");
-        a.sk_in0 = d->d_skip_in0; a.sk_in1 = d->d_skip_in1; a.sk_c0 = d->skip_c0; a.sk_cin = scin;
-        a.sk_w16 = reinterpret_cast<const uint4*>(d->d_skip_w16); a.sk_bias = d->d_skip_bias;
-        a.sk_amax0 = d->d_skip_amax0; a.sk_amax1 = d->skip_c1 > 0 ? d->d_skip_amax1 : nullptr;
-    }
-    if (slices > 1) {
-        a.partial = static_cast<float*>(d->d_workspace);
-        a.chunks_per_slice = (cin / 16 + slices - 1) / slices;
-        a.stats = nullptr; a.out_amax = nullptr;   // the conv kernel writes raw slices; the reduce takes the statistics
-    }
-
-    size_t lds = (size_t)4 * a.CS * sizeof(uint4);
-    PX_REQUIRE(lds <= 160 * 1024, "f16x3 conv: tile needs %zu B of LDS", lds);
-    if (conv16_epi_lds(MB, NB, slices)) { a.epi_lds = 1; lds = std::max(lds, conv16_epi_bytes(MB, NB)); }   // room for the transposing epilogue
-    const dim3 grid((unsigned)a.n_tiles, (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)), (unsigned)slices);
-    if (slices > 1) {
-        int rc = 1;
-        if (sp) {
-            rc = (MB == 2) ? launch_subpixel<2>(a, lds, grid, st) : launch_subpixel<1>(a, lds, grid, st);
+        const long ovol = (long)p.OD * p.OH * p.OW;
+        int MB = (p.coutp >= 64) ? 2 : 1;
+        int NB = (s.stride == 2) ? 1 : 4;   // stride 2: the tile holds 8x the voxels it produces; only NB = 1 fits (112 KB, one workgroup per CU)
+        auto n_wg = [&](int mb, int nb) {
+            const long tiles = (ovol + 128L * nb - 1) / (128L * nb);
+            return tiles * ((p.coutp + mb * 32 - 1) / (mb * 32));
+        };
+        // Split-K (needs the caller's workspace): when the output is too small to give every CU two workgroups, keep the
+        // big MFMA-efficient tile and split the channel chunks over up to 8 slices instead of shrinking the tile; the
+        // slices write partial outputs that splitk_reduce_kernel adds in a fixed order.
+        int slices = 1;
+        if (smax >= 2 && n_wg(MB, NB) < 512) {
+            bool found = false;
+            for (int nb = NB; nb >= 1 && !found; nb /= 2) {
+                for (int sl = 1; sl <= smax; sl *= 2)
+                    if (n_wg(MB, nb) * sl >= 512) { NB = nb; slices = sl; found = true; break; }
+            }
+            if (!found) { NB = 1; slices = 1; while (slices * 2 <= smax) slices *= 2; }
         } else {
-#define PX_CONV16_SK(KS_, MB_, NB_) \
-            if (d->ksize == KS_ && MB == MB_ && NB == NB_) rc = launch_f16x3<KS_, MB_, NB_>(a, lds, grid, st);
-            PX_CONV16_SK(3, 2, 4) PX_CONV16_SK(3, 2, 2) PX_CONV16_SK(3, 2, 1) PX_CONV16_SK(3, 1, 4) PX_CONV16_SK(3, 1, 2) PX_CONV16_SK(3, 1, 1)
-            PX_CONV16_SK(1, 2, 4) PX_CONV16_SK(1, 2, 2) PX_CONV16_SK(1, 2, 1) PX_CONV16_SK(1, 1, 4) PX_CONV16_SK(1, 1, 2) PX_CONV16_SK(1, 1, 1)
-#undef PX_CONV16_SK
+            while (n_wg(MB, NB) < 512 && NB > 1) NB /= 2;
+            if (n_wg(MB, NB) < 512 && MB > 1) MB = 1;
         }
-        if (rc) return rc;
-        const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
-        if (d->d_out_stats) {
-            const dim3 rgrid((unsigned)reduce_segments(osp), (unsigned)a.cout);
-            double* rstats = reinterpret_cast<double*>(d->d_out_stats);
-            PX_REQUIRE((reinterpret_cast<size_t>(rstats) & 7) == 0, "f16x3 conv: d_out_stats of a split-K launch must be 8-byte aligned");
-            const bool vec = osp % 4 == 0 && ((reinterpret_cast<size_t>(a.partial) | reinterpret_cast<size_t>(a.residual) | reinterpret_cast<size_t>(a.out)) & 15) == 0;
-            if (vec) hipLaunchKernelGGL(splitk_reduce_stats_kernel<true>, rgrid, dim3(256), 0, st, a.partial, slices, n_elems, osp, a.bias, a.residual,
-                                        a.out, rstats, d->d_out_amax);
-            else hipLaunchKernelGGL(splitk_reduce_stats_kernel<false>, rgrid, dim3(256), 0, st, a.partial, slices, n_elems, osp, a.bias, a.residual,
-                                    a.out, rstats, d->d_out_amax);
-        } else {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, slices, n_elems, osp,
-                               a.bias, a.residual, a.out);
-        }
-        PX_CHECK_HIP(hipGetLastError());
-        return 0;
+        p.MB = MB; p.NB = NB; p.slices = slices;
+        tile(p.OD, p.OH, p.OW, 128 * NB);
+        p.HX = (p.TX - 1) * s.stride + s.ksize; p.HY = (p.TY - 1) * s.stride + s.ksize; p.HZ = (p.TZ - 1) * s.stride + s.ksize;
     }
-    if (sp) return (MB == 2) ? launch_subpixel<2>(a, lds, grid, st) : launch_subpixel<1>(a, lds, grid, st);
-    if (d->ksize == 3 && MB == 2 && NB == 4 && cin == 64 && d->c_out == 64 && d->stride == 1 && !d->upsample && d->c1 == 0 && !a.sk_w16 &&
-        (long)a.OD * a.OH * a.OW >= 128L * 128 * 128) {
-        auto kern = conv3d_f16x3_c64_fullres_kernel;
-        PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-        PX_CHECK_HIP(hipGetLastError());
-        return 0;
+    p.HYX = p.HY * p.HX; p.CS = p.HZ * p.HYX;
+    p.mHX = magic_of(p.HX); p.mHYX = magic_of(p.HYX);
+    if (p.slices > 1) p.chunks_per_slice = (chunks + p.slices - 1) / p.slices;
+    p.lds_bytes = (size_t)4 * p.CS * sizeof(uint4);   // four 16-byte fp16 planes per halo voxel (exact: 16 fp32 planes)
+    if (p.lds_bytes > 160 * 1024) return refuse(CONV_BAD_LDS);
+    // LDS the transposing epilogue needs (4 waves x 32 rows x (NB*32 + 4) floats + the statistics partials), and whether the launch
+    // gets it: unsplit launches only, as long as two workgroups still fit on a CU
+    const size_t epi_bytes = ((size_t)4 * 32 * (p.NB * 32 + 4) + (size_t)4 * p.MB * 32 * 2) * sizeof(float);
+    if (p.slices == 1 && epi_bytes <= 80 * 1024) { p.epi_lds = 1; p.lds_bytes = std::max(p.lds_bytes, epi_bytes); }
+    p.grid = dim3((unsigned)p.n_tiles, (unsigned)((p.coutp + p.MB * 32 - 1) / (p.MB * 32)), (unsigned)p.slices);
+    if (!p.f16x3()) return p;
+    // where the launch leaves its partial statistics (d_out_stats): per tile in fp32, or per reduce segment in fp64
+    const long osp = (long)p.OD * p.OH * p.OW;
+    if (p.slices > 1) {
+        const int n = reduce_segments(osp);
+        p.stats = ConvStatLayout{n, n, 1, 1};
+        p.stats_floats = (int64_t)s.c_out * n * 2 * (int64_t)(sizeof(double) / sizeof(float));
+        p.workspace_bytes = (int64_t)p.slices * s.c_out * osp * (int64_t)sizeof(float);
+    } else {
+        p.stats = ConvStatLayout{p.n_tiles, 1, p.coutp, 0};
+        p.stats_floats = (int64_t)p.n_tiles * p.coutp * 2;
     }
-#define PX_CONV16_CASE(KS_, MB_, NB_) \
-    if (d->ksize == KS_ && MB == MB_ && NB == NB_) return launch_f16x3<KS_, MB_, NB_>(a, lds, grid, st);
-    PX_CONV16_CASE(3, 2, 4) PX_CONV16_CASE(3, 2, 2) PX_CONV16_CASE(3, 2, 1)
-    PX_CONV16_CASE(3, 1, 4) PX_CONV16_CASE(3, 1, 2) PX_CONV16_CASE(3, 1, 1)
-    PX_CONV16_CASE(1, 2, 4) PX_CONV16_CASE(1, 2, 2) PX_CONV16_CASE(1, 2, 1)
-    PX_CONV16_CASE(1, 1, 4) PX_CONV16_CASE(1, 1, 2) PX_CONV16_CASE(1, 1, 1)
-#undef PX_CONV16_CASE
-    return set_error("f16x3 conv: no kernel variant for ksize=%d MB=%d NB=%d", d->ksize, MB, NB);
+    // the full-resolution 64 -> 64 layers: the <3,2,4> code under its own symbol
+    p.fullres = !sub && p.slices == 1 && s.ksize == 3 && p.MB == 2 && p.NB == 4 && cin == 64 && s.c_out == 64 && s.stride == 1 && !s.upsample &&
+                s.c1 == 0 && !s.skip && osp >= 128L * 128 * 128;
+    const int scin = s.skip_c0 + s.skip_c1;
+    p.skip_foldable = !sub && s.stride == 1 && !s.upsample && scin > 0 && scin % 16 == 0 && s.skip_c0 % 8 == 0 && p.slices == 1;
+    return p;
 }
 
-template <int KS, int MB, int NB>
-static int launch_exact(const Conv16Args& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
-    auto kern = conv3d_exact_kernel<KS, MB, NB>;
+// the kernel of a tiled plan: one table for the f16x3 and the exact instantiations
+using ConvKernel = void (*)(Conv16Args);
+static ConvKernel conv16_kernel(const ConvPlan& p) {
+    if (p.path == CONV_F16X3_SUBPIXEL) return p.MB == 2 ? conv3d_f16x3_subpixel_kernel<2> : conv3d_f16x3_subpixel_kernel<1>;
+    if (p.fullres) return conv3d_f16x3_c64_fullres_kernel;
+#define PX_CONV16_PICK(KS_, MB_, NB_) \
+    if (p.KS == KS_ && p.MB == MB_ && p.NB == NB_) return p.path == CONV_EXACT_TILED ? conv3d_exact_kernel<KS_, MB_, NB_> : conv3d_f16x3_kernel<KS_, MB_, NB_>;
+    PX_CONV_VARIANTS(PX_CONV16_PICK)
+#undef PX_CONV16_PICK
+    return nullptr;
+}
+
+static int launch(ConvKernel kern, const ConvPlan& p, const Conv16Args& a, hipStream_t st) {
+    PX_REQUIRE(kern != nullptr, "conv: no kernel variant for ksize=%d MB=%d NB=%d", p.KS, p.MB, p.NB);
     PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
+    hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds_bytes, st, a);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// 1 when pixie_conv3d_forward sends an exact-fp32 descriptor (d_w, no d_w16) through the tiled body above instead of the
-// first-generation kernel of conv3d_mfma.hip (odd channel counts, tiny test networks)
-bool conv3d_exact_tiled_ok(const pixie_conv_desc* d) {
-    const int cin = d->c0 + d->c1;
-    return cin % 16 == 0 && (d->stride == 1 || (d->stride == 2 && d->ksize == 3 && !d->upsample)) && getenv("PIXIE_CONV_EXACT_V1") == nullptr;
-}
-
-// called by pixie_conv3d_forward (conv3d_mfma.hip) for exact-fp32 descriptors that conv3d_exact_tiled_ok accepts
-int conv3d_exact_forward(const pixie_conv_desc* d, hipStream_t st) {
+// the plan's geometry and the operands both tiled paths share
+static Conv16Args conv16_args(const pixie_conv_desc* d, const ConvPlan& p) {
     Conv16Args a{};
     a.in0 = d->d_in0; a.in1 = d->d_in1; a.c0 = d->c0; a.cin = d->c0 + d->c1;
+    a.ID = d->in_d; a.IH = d->in_h; a.IW = d->in_w;
+    a.LD = p.LD; a.LH = p.LH; a.LW = p.LW; a.ups = p.ups; a.stride = d->stride;
+    a.OD = p.OD; a.OH = p.OH; a.OW = p.OW;
     a.pro_a = d->d_pro_a; a.pro_b = d->d_pro_b; a.gamma = d->d_gamma; a.beta = d->d_beta; a.act = d->act;
-    a.wf = d->d_w; a.bias = d->d_bias;
+    a.bias = d->d_bias; a.cout = d->c_out; a.coutp = p.coutp;
     a.residual = d->d_residual; a.out = d->d_out;
+    a.TX = p.TX; a.TY = p.TY; a.TZ = p.TZ; a.lTX = p.lTX; a.lTY = p.lTY;
+    a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.tiles_z = p.tiles_z; a.n_tiles = p.n_tiles;
+    a.HX = p.HX; a.HY = p.HY; a.HZ = p.HZ; a.HYX = p.HYX; a.CS = p.CS; a.mHX = p.mHX; a.mHYX = p.mHYX;
+    a.chunks_per_slice = p.chunks_per_slice; a.epi_lds = p.epi_lds;
+    return a;
+}
+
+// called by pixie_conv3d_forward (conv3d_mfma.hip) when the descriptor carries f16x2-packed weights
+int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_t st) {
+    PX_REQUIRE(p.refusal != CONV_BAD_STRIDE, "f16x3 conv: stride must be 1, or 2 for a 3^3 kernel");
+    PX_REQUIRE(p.refusal != CONV_BAD_CHANNELS, "f16x3 conv: c_in must be a multiple of 16 (got %d+%d)", d->c0, d->c1);
+    PX_REQUIRE(d->d_in_amax0 != nullptr || d->in_bound > 0.0f, "f16x3 conv: needs d_in_amax0 or a positive in_bound");
+    PX_REQUIRE(d->c1 == 0 || d->d_in_amax0 == nullptr || d->d_in_amax1 != nullptr, "f16x3 conv: second input needs its own amax slot");
+    PX_REQUIRE(p.refusal != CONV_BAD_SUBPIXEL, "f16x3 conv: sub-pixel weights need upsample = 1, ksize = 3, stride = 1 and no folded skip");
+    Conv16Args a = conv16_args(d, p);
+    a.w16 = reinterpret_cast<const uint4*>(d->d_w16);
+    a.amax0 = d->d_in_amax0; a.amax1 = (d->c1 > 0) ? d->d_in_amax1 : nullptr; a.in_bound = d->in_bound;
+    a.stats = d->d_out_stats; a.out_amax = d->d_out_amax;
+    if (d->d_skip_w16) {
+        PX_REQUIRE(p.skip_foldable, "f16x3 conv: this launch cannot fold a skip convolution (pixie_conv_skip_foldable)");
+        PX_REQUIRE(d->d_skip_in0 && d->d_skip_amax0 && (d->skip_c1 == 0 || (d->d_skip_in1 && d->d_skip_amax1)), "f16x3 conv: folded skip needs its inputs and their amax slots");
+        a.sk_in0 = d->d_skip_in0; a.sk_in1 = d->d_skip_in1; a.sk_c0 = d->skip_c0; a.sk_cin = d->skip_c0 + d->skip_c1;
+        a.sk_w16 = reinterpret_cast<const uint4*>(d->d_skip_w16); a.sk_bias = d->d_skip_bias;
+        a.sk_amax0 = d->d_skip_amax0; a.sk_amax1 = d->skip_c1 > 0 ? d->d_skip_amax1 : nullptr;
+    }
+    if (p.slices > 1) {
+        a.partial = static_cast<float*>(d->d_workspace);
+        a.stats = nullptr; a.out_amax = nullptr;   // the conv kernel writes raw slices; the reduce takes the statistics
+    }
+    PX_REQUIRE(p.refusal != CONV_BAD_LDS, "f16x3 conv: tile needs %zu B of LDS", p.lds_bytes);
+    PX_REQUIRE(p.f16x3(), "f16x3 conv: bad sizes");
+    if (int rc = launch(conv16_kernel(p), p, a, st)) return rc;
+    if (p.slices == 1) return 0;
+    const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
+    if (d->d_out_stats) {
+        const dim3 rgrid((unsigned)reduce_segments(osp), (unsigned)a.cout);
+        double* rstats = reinterpret_cast<double*>(d->d_out_stats);
+        PX_REQUIRE((reinterpret_cast<size_t>(rstats) & 7) == 0, "f16x3 conv: d_out_stats of a split-K launch must be 8-byte aligned");
+        const bool vec = osp % 4 == 0 && ((reinterpret_cast<size_t>(a.partial) | reinterpret_cast<size_t>(a.residual) | reinterpret_cast<size_t>(a.out)) & 15) == 0;
+        if (vec) hipLaunchKernelGGL(splitk_reduce_stats_kernel<true>, rgrid, dim3(256), 0, st, a.partial, p.slices, n_elems, osp, a.bias, a.residual,
+                                    a.out, rstats, d->d_out_amax);
+        else hipLaunchKernelGGL(splitk_reduce_stats_kernel<false>, rgrid, dim3(256), 0, st, a.partial, p.slices, n_elems, osp, a.bias, a.residual,
+                                a.out, rstats, d->d_out_amax);
+    } else {
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, p.slices, n_elems, osp,
+                           a.bias, a.residual, a.out);
+    }
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// called by pixie_conv3d_forward (conv3d_mfma.hip) for exact-fp32 descriptors (d_w, no d_w16) that the plan sends through the
+// tiled body above instead of the first-generation kernel
+int conv3d_exact_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_t st) {
+    PX_REQUIRE(p.refusal != CONV_BAD_LDS, "exact conv: tile needs %zu B of LDS", p.lds_bytes);
+    PX_REQUIRE(p.path == CONV_EXACT_TILED, "exact conv: bad sizes");
+    Conv16Args a = conv16_args(d, p);
+    a.wf = d->d_w;
     a.in_bound = 1.0f;
-    int MB = 0, NB = 0;
-    conv16_exact_tiling(d, a, MB, NB);
-    size_t lds = (size_t)4 * a.CS * sizeof(uint4);      // 16 fp32 planes = the four 16-byte fp16 planes
-    PX_REQUIRE(lds <= 160 * 1024, "exact conv: tile needs %zu B of LDS", lds);
-    if (conv16_epi_lds(MB, NB, 1)) { a.epi_lds = 1; lds = std::max(lds, conv16_epi_bytes(MB, NB)); }   // room for the transposing epilogue
-    const dim3 grid((unsigned)a.n_tiles, (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)), 1u);
-#define PX_CONVEX_CASE(KS_, MB_, NB_) \
-    if (d->ksize == KS_ && MB == MB_ && NB == NB_) return launch_exact<KS_, MB_, NB_>(a, lds, grid, st);
-    PX_CONVEX_CASE(3, 2, 4) PX_CONVEX_CASE(3, 2, 2) PX_CONVEX_CASE(3, 2, 1)
-    PX_CONVEX_CASE(3, 1, 4) PX_CONVEX_CASE(3, 1, 2) PX_CONVEX_CASE(3, 1, 1)
-    PX_CONVEX_CASE(1, 2, 4) PX_CONVEX_CASE(1, 2, 2) PX_CONVEX_CASE(1, 2, 1)
-    PX_CONVEX_CASE(1, 1, 4) PX_CONVEX_CASE(1, 1, 2) PX_CONVEX_CASE(1, 1, 1)
-#undef PX_CONVEX_CASE
-    return set_error("exact conv: no kernel variant for ksize=%d MB=%d NB=%d", d->ksize, MB, NB);
+    return launch(conv16_kernel(p), p, a, st);
 }
 
 }  // namespace pixie
 
 using namespace pixie;
 
+static ConvPlan plan_of(const pixie_conv_desc* d) { return d ? conv_plan(conv_shape_of(d)) : ConvPlan{}; }
+static StatParts stat_parts(const ConvPlan& p, const void* stats) { return StatParts{stats, p.stats.n, p.stats.cstride, p.stats.tstride, p.stats.f64}; }
+
 // number of floats of the epilogue statistics buffer for this descriptor (0 if the layer does not take the f16x3 path)
-extern "C" int64_t pixie_conv_stats_floats(const pixie_conv_desc* d) {
-    if (!d || !d->d_w16 || !(d->stride == 1 || (d->stride == 2 && d->ksize == 3)) || (d->ksize != 1 && d->ksize != 3)) return 0;
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(d, a, MB, NB, &slices);
-    if (slices > 1) return (int64_t)a.cout * reduce_segments((long)a.OD * a.OH * a.OW) * 2 * (int64_t)(sizeof(double) / sizeof(float));
-    return (int64_t)a.n_tiles * a.coutp * 2;
-}
+extern "C" int64_t pixie_conv_stats_floats(const pixie_conv_desc* d) { return plan_of(d).stats_floats; }
 
 // bytes of d_workspace this layer can use for split-K (0: it would not split).  Decided on the shape alone.
 extern "C" int64_t pixie_conv_workspace_bytes(const pixie_conv_desc* d) {
-    if (!d || !d->d_w16 || !(d->stride == 1 || (d->stride == 2 && d->ksize == 3)) || (d->ksize != 1 && d->ksize != 3)) return 0;
-    pixie_conv_desc probe = *d;
-    probe.d_workspace = reinterpret_cast<void*>(1);   // "a workspace would be available"
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(&probe, a, MB, NB, &slices);
-    return slices > 1 ? (int64_t)slices * a.cout * a.OD * a.OH * a.OW * (int64_t)sizeof(float) : 0;
+    if (!d) return 0;
+    ConvShape s = conv_shape_of(d);
+    s.workspace = true;   // "a workspace would be available"
+    return conv_plan(s).workspace_bytes;
 }
 
 // which kernel instantiation pixie_conv3d_forward picks for this descriptor: variant = ksize * 100 + MB * 10 + NB of
@@ -1251,61 +1208,43 @@ extern "C" int64_t pixie_conv_workspace_bytes(const pixie_conv_desc* d) {
 // its own per-launch timings the way rocprofv3 groups them: by kernel name.)
 #ifdef PIXIE_DIAG
 extern "C" int pixie_conv_kernel_variant(const pixie_conv_desc* d, int* slices_out) {
-    if (slices_out) *slices_out = 1;
-    if (!d || !d->d_w16 || !(d->stride == 1 || (d->stride == 2 && d->ksize == 3)) || (d->ksize != 1 && d->ksize != 3)) return 0;
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(d, a, MB, NB, &slices);
-    if (slices_out) *slices_out = slices;
-    if (conv16_subpixel(d)) return 8300 + MB * 10 + NB;   // conv3d_f16x3_subpixel_kernel<MB>
-    if (d->ksize == 3 && MB == 2 && NB == 4 && d->c0 + d->c1 == 64 && d->c_out == 64 && d->stride == 1 && !d->upsample && d->c1 == 0 && !d->d_skip_w16 &&
-        (long)a.OD * a.OH * a.OW >= 128L * 128 * 128)
-        return 9324;   // conv3d_f16x3_c64_fullres_kernel: the <3,2,4> code under its own symbol
-    return d->ksize * 100 + MB * 10 + NB;
+    const ConvPlan p = plan_of(d);
+    if (slices_out) *slices_out = p.f16x3() ? p.slices : 1;
+    if (!p.f16x3()) return 0;
+    if (p.path == CONV_F16X3_SUBPIXEL) return 8300 + p.MB * 10 + p.NB;   // conv3d_f16x3_subpixel_kernel<MB>
+    if (p.fullres) return 9324;                                           // conv3d_f16x3_c64_fullres_kernel
+    return p.KS * 100 + p.MB * 10 + p.NB;
 }
 
 // the tiling pixie_conv3d_forward launches this descriptor with: out = TX, TY, TZ, tiles_x, tiles_y, tiles_z, epi_lds, slices,
 // MB, NB.  With d_w16 the f16x3 launch (sub-pixel: the tile lies over the STORED voxels, each tile is four workgroups);
 // without, the exact-fp32 launch of the same body.  Returns 1 (and leaves out alone) for descriptors that take neither.
 extern "C" int pixie_conv_tile_geometry(const pixie_conv_desc* d, int32_t out[10]) {
-    if (!d || !out || (d->ksize != 1 && d->ksize != 3) || !(d->stride == 1 || (d->stride == 2 && d->ksize == 3 && !d->upsample))) return 1;
-    if ((d->c0 + d->c1) % 16 != 0 || (d->d_w16 && d->c0 % 8 != 0)) return 1;
-    if (!d->d_w16 && !conv3d_exact_tiled_ok(d)) return 1;
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    if (d->d_w16) conv16_tiling(d, a, MB, NB, &slices);
-    else conv16_exact_tiling(d, a, MB, NB);
-    const int32_t v[10] = {a.TX, a.TY, a.TZ, a.tiles_x, a.tiles_y, a.tiles_z, conv16_epi_lds(MB, NB, slices) ? 1 : 0, slices, MB, NB};
+    const ConvPlan p = plan_of(d);
+    if (!out || !p.tiled()) return 1;
+    const int32_t v[10] = {p.TX, p.TY, p.TZ, p.tiles_x, p.tiles_y, p.tiles_z, p.epi_lds, p.slices, p.MB, p.NB};
     for (int i = 0; i < 10; ++i) out[i] = v[i];
     return 0;
 }
 
-// where this descriptor's launch leaves its partial statistics, as pixie_stats_finalize / pixie_stats_norm_finalize will read them
-// (conv16_stat_parts): out = partials per channel, cstride, tstride (in (sum, sum of squares) pairs), 1 = fp64 reduce segments /
+// where this descriptor's launch leaves its partial statistics, as pixie_stats_finalize / pixie_stats_norm_finalize will read them:
+// out = partials per channel, cstride, tstride (in (sum, sum of squares) pairs), 1 = fp64 reduce segments /
 // 0 = fp32 tile partials, voxels per reduce segment (0 for tile partials), c_out padded.  Returns 1 off the f16x3 path.
 extern "C" int pixie_conv_stats_layout(const pixie_conv_desc* d, int64_t out[6]) {
-    if (!out || pixie_conv_stats_floats(d) <= 0) return 1;
-    const StatParts p = conv16_stat_parts(d, nullptr);
-    out[0] = p.n; out[1] = p.cstride; out[2] = p.tstride; out[3] = p.f64; out[4] = p.f64 ? kReduceSeg : 0;
-    out[5] = pixie_conv_cout_padded(d->c_out);
+    const ConvPlan p = plan_of(d);
+    if (!out || !p.f16x3()) return 1;
+    out[0] = p.stats.n; out[1] = p.stats.cstride; out[2] = p.stats.tstride; out[3] = p.stats.f64; out[4] = p.stats.f64 ? kReduceSeg : 0;
+    out[5] = p.coutp;
     return 0;
 }
 #endif
 
-extern "C" int pixie_conv_skip_foldable(const pixie_conv_desc* d) {
-    if (!d || !d->d_w16 || d->stride != 1 || d->upsample || (d->ksize != 1 && d->ksize != 3)) return 0;
-    const int scin = d->skip_c0 + d->skip_c1;
-    if (scin <= 0 || scin % 16 != 0 || d->skip_c0 % 8 != 0 || (d->c0 + d->c1) % 16 != 0 || d->c0 % 8 != 0) return 0;
-    Conv16Args a{};
-    int MB = 0, NB = 0, slices = 1;
-    conv16_tiling(d, a, MB, NB, &slices);
-    return slices == 1 ? 1 : 0;
-}
+extern "C" int pixie_conv_skip_foldable(const pixie_conv_desc* d) { return plan_of(d).skip_foldable ? 1 : 0; }
 
 extern "C" int pixie_stats_finalize(const float* d_stats, const pixie_conv_desc* d, double* d_sums, void* stream) {
     PX_REQUIRE(d_stats && d && d_sums, "pixie_stats_finalize: null argument");
-    // the tile (or segment) count is recomputed exactly as conv3d_f16x3_forward computes it
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), conv16_stat_parts(d, d_stats), d_sums);
+    // the tile (or segment) count comes from the plan conv3d_f16x3_forward launched with
+    hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), stat_parts(plan_of(d), d_stats), d_sums);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1320,8 +1259,8 @@ extern "C" int pixie_stats_norm_finalize(const float* d_stats0, const pixie_conv
     PX_REQUIRE(!d_stats1 || desc1->c_out == c1, "pixie_stats_norm_finalize: desc1 has %d output channels, c1 is %d", desc1 ? desc1->c_out : 0, c1);
     PX_REQUIRE(mode == 0 || (mode == 1 && groups > 0 && channels % groups == 0), "pixie_stats_norm_finalize: bad mode/groups");
     const StatParts none{nullptr, 0, 0, 0, 0};
-    const StatParts p0 = d_stats0 ? conv16_stat_parts(desc0, d_stats0) : none;
-    const StatParts p1 = d_stats1 ? conv16_stat_parts(desc1, d_stats1) : none;
+    const StatParts p0 = d_stats0 ? stat_parts(plan_of(desc0), d_stats0) : none;
+    const StatParts p1 = d_stats1 ? stat_parts(plan_of(desc1), d_stats1) : none;
     hipLaunchKernelGGL(stats_norm_finalize_kernel, dim3((unsigned)(mode == 0 ? channels : groups)), dim3(256), 0, as_stream(stream), p0, d_sums0, c0,
                        p1, d_sums1, channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
     PX_CHECK_HIP(hipGetLastError());

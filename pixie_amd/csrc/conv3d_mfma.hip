@@ -23,6 +23,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "conv_plan.h"
 
 namespace pixie {
 
@@ -211,10 +212,6 @@ __global__ void pack_weights_kernel(const float* __restrict__ src, float* __rest
     dst[i] = (co < cout) ? src[((long)co * cin + ci) * taps + tap] : 0.0f;
 }
 
-static unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-static int pow2_le(int v, int cap) { int p = 1; while (p * 2 <= v && p * 2 <= cap) p *= 2; return p; }
-
 template <int KS, int MB, int NB, int CK>
 static int launch_variant(const ConvArgs& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
     auto kern = conv3d_mfma_kernel<KS, MB, NB, CK>;
@@ -226,11 +223,6 @@ static int launch_variant(const ConvArgs& a, size_t lds_bytes, dim3 grid, hipStr
 
 }  // namespace pixie
 
-namespace pixie {
-int conv3d_f16x3_forward(const pixie_conv_desc* d, hipStream_t st);
-bool conv3d_exact_tiled_ok(const pixie_conv_desc* d);
-int conv3d_exact_forward(const pixie_conv_desc* d, hipStream_t st);
-}
 using namespace pixie;
 
 extern "C" int pixie_conv_cout_padded(int c_out) { return (c_out + 31) / 32 * 32; }
@@ -258,25 +250,19 @@ extern "C" int pixie_conv3d_forward(const pixie_conv_desc* d, void* stream) {
     PX_REQUIRE(!(d->d_gamma && d->upsample) || (d->d_w16 && d->w16_subpixel),
                "pixie_conv3d_forward: spatial affine with upsample needs the sub-pixel path (w16_subpixel), with gamma/beta of the stored grid");
 
-    if (d->d_w16) return conv3d_f16x3_forward(d, as_stream(stream));
+    const ConvPlan p = conv_plan(conv_shape_of(d));
+    if (d->d_w16) return conv3d_f16x3_forward(d, p, as_stream(stream));
     PX_REQUIRE(!d->d_skip_w16, "pixie_conv3d_forward: a folded skip convolution needs the f16x3 path (d_w16)");
     // 16-aligned channel counts (every layer of the reference networks): the tiled body of conv3d_f16x3.hip with fp32
     // operands; the kernel below keeps the odd shapes (tiny test networks, c_in = 3 ...)
-    if (conv3d_exact_tiled_ok(d)) return conv3d_exact_forward(d, as_stream(stream));
+    if (p.path != CONV_FIRST_GEN) return conv3d_exact_forward(d, p, as_stream(stream));
 
     ConvArgs a{};
     a.in0 = d->d_in0; a.in1 = d->d_in1; a.c0 = d->c0; a.cin = d->c0 + d->c1;
     a.ID = d->in_d; a.IH = d->in_h; a.IW = d->in_w;
-    a.ups = d->upsample;
-    a.LD = a.ID << a.ups; a.LH = a.IH << a.ups; a.LW = a.IW << a.ups;
+    a.ups = p.ups; a.LD = p.LD; a.LH = p.LH; a.LW = p.LW;
     a.stride = d->stride;
-    const int pad = d->ksize == 3 ? 1 : 0;
-    a.OD = (a.LD + 2 * pad - d->ksize) / a.stride + 1;
-    a.OH = (a.LH + 2 * pad - d->ksize) / a.stride + 1;
-    a.OW = (a.LW + 2 * pad - d->ksize) / a.stride + 1;
-    if (d->out_d > 0) a.OD = std::min(a.OD, (int)d->out_d);   // odd-grid crop (diffusion_network.py:925-930)
-    if (d->out_h > 0) a.OH = std::min(a.OH, (int)d->out_h);
-    if (d->out_w > 0) a.OW = std::min(a.OW, (int)d->out_w);
+    a.OD = p.OD; a.OH = p.OH; a.OW = p.OW;
     a.pro_a = d->d_pro_a; a.pro_b = d->d_pro_b; a.gamma = d->d_gamma; a.beta = d->d_beta; a.act = d->act;
     a.w = d->d_w; a.bias = d->d_bias; a.cout = d->c_out; a.coutp = pixie_conv_cout_padded(d->c_out);
     a.residual = d->d_residual; a.out = d->d_out;
@@ -311,12 +297,9 @@ extern "C" int pixie_conv3d_forward(const pixie_conv_desc* d, void* stream) {
     const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.tiles_z), (unsigned)((a.coutp + MB * 32 - 1) / (MB * 32)));
     hipStream_t st = as_stream(stream);
 
-#define PX_CONV_CASE(KS_, MB_, NB_, CK_) \
-    if (d->ksize == KS_ && MB == MB_ && NB == NB_) return launch_variant<KS_, MB_, NB_, CK_>(a, lds, grid, st);
-    PX_CONV_CASE(3, 2, 4, 4) PX_CONV_CASE(3, 2, 2, 4) PX_CONV_CASE(3, 2, 1, 4)
-    PX_CONV_CASE(3, 1, 4, 4) PX_CONV_CASE(3, 1, 2, 4) PX_CONV_CASE(3, 1, 1, 4)
-    PX_CONV_CASE(1, 2, 4, 16) PX_CONV_CASE(1, 2, 2, 16) PX_CONV_CASE(1, 2, 1, 16)
-    PX_CONV_CASE(1, 1, 4, 16) PX_CONV_CASE(1, 1, 2, 16) PX_CONV_CASE(1, 1, 1, 16)
+#define PX_CONV_CASE(KS_, MB_, NB_) \
+    if (d->ksize == KS_ && MB == MB_ && NB == NB_) return launch_variant<KS_, MB_, NB_, (KS_ == 3 ? 4 : 16)>(a, lds, grid, st);
+    PX_CONV_VARIANTS(PX_CONV_CASE)
 #undef PX_CONV_CASE
     return set_error("pixie_conv3d_forward: no kernel variant for ksize=%d MB=%d NB=%d", d->ksize, MB, NB);
 }

@@ -29,6 +29,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "conv_plan.h"
 
 namespace pixie {
 // internal entry points of unet_ops.hip (the launches of pixie_channel_stats / pixie_norm_finalize without their set-up work)
@@ -408,20 +409,21 @@ struct Exec {
         return r;
     }
 
-    bool f16_ok(const std::vector<TP>& parts, int stride) const {    // unet.py: HipOps.f16x3_ok
-        int cin = 0;
-        for (auto& t : parts) cin += t->c;
-        return net->cfg.precision == 0 && (stride == 1 || stride == 2) && cin % 16 == 0 && parts[0]->c % 8 == 0;
+    // The plan of a launch over th.cat(parts): the f16x3 path where the network's precision asks for it and the shape allows it
+    // (unet.py: HipOps.f16x3_ok), else exact fp32.  The caller sets the sub-pixel, crop and skip fields of s first.
+    ConvPlan plan_conv(ConvShape& s, const std::vector<TP>& parts, int cout, int ksize, int stride, bool upsample) const {
+        s.c0 = parts[0]->c; s.c1 = parts.size() > 1 ? parts[1]->c : 0; s.c_out = cout;
+        s.in_d = parts[0]->d; s.in_h = parts[0]->h; s.in_w = parts[0]->w;
+        s.ksize = ksize; s.stride = stride; s.upsample = upsample ? 1 : 0;
+        s.w16 = net->cfg.precision == 0; s.workspace = net->split_k; s.exact_v1 = conv_exact_v1();
+        ConvPlan p = conv_plan(s);
+        if (p.refusal == CONV_BAD_CHANNELS) { s.w16 = s.subpixel = s.skip = false; p = conv_plan(s); }
+        return p;
     }
     bool skip_foldable(const TP& x, int cout, int ksize, const std::vector<TP>& sp) const {   // unet.py: HipOps.skip_foldable
-        pixie_conv_desc d;
-        std::memset(&d, 0, sizeof d);
-        d.c0 = x->c; d.in_d = x->d; d.in_h = x->h; d.in_w = x->w;
-        d.stride = 1; d.ksize = ksize; d.c_out = cout;
-        d.d_w16 = reinterpret_cast<const void*>(0x100);
-        d.d_workspace = net->split_k ? reinterpret_cast<void*>(0x100) : nullptr;
-        d.skip_c0 = sp[0]->c; d.skip_c1 = sp.size() > 1 ? sp[1]->c : 0;
-        return pixie_conv_skip_foldable(&d) != 0;
+        ConvShape s;
+        s.skip_c0 = sp[0]->c; s.skip_c1 = sp.size() > 1 ? sp[1]->c : 0;
+        return plan_conv(s, {x}, cout, ksize, 1, false).skip_foldable;
     }
 
     // ---- one convolution launch (unet.py: UNetRunner._conv + HipOps.conv) ----
@@ -436,17 +438,16 @@ struct Exec {
     TP conv(const std::vector<TP>& parts, const std::string& wkey, int cout, int ksize, const ConvOpt& o) {
         const TP& x0 = parts[0];
         const Tens* x1 = parts.size() > 1 ? parts[1].get() : nullptr;
-        const int up = o.upsample ? 2 : 1, pad = ksize == 3 ? 1 : 0;
-        int od = (x0->d * up + 2 * pad - ksize) / o.stride + 1;
-        int oh = (x0->h * up + 2 * pad - ksize) / o.stride + 1;
-        int ow = (x0->w * up + 2 * pad - ksize) / o.stride + 1;
+        ConvShape s;
+        s.out_d = o.out_d; s.out_h = o.out_h; s.out_w = o.out_w;   // odd-grid crop (diffusion_network.py:925-930): the cropped voxels are never computed
+        s.subpixel = net->subpixel && o.upsample && ksize == 3 && o.stride == 1;   // unet.py: UNetRunner._conv
+        if (o.skip_parts) { s.skip = true; s.skip_c0 = (*o.skip_parts)[0]->c; s.skip_c1 = o.skip_parts->size() > 1 ? (*o.skip_parts)[1]->c : 0; }
+        const ConvPlan plan = plan_conv(s, parts, cout, ksize, o.stride, o.upsample);
+        const int od = plan.OD, oh = plan.OH, ow = plan.OW;
         pixie_conv_desc desc;
         std::memset(&desc, 0, sizeof desc);
-        if (o.out_d) {   // odd-grid crop (diffusion_network.py:925-930): the cropped voxels are never computed
-            od = std::min(od, o.out_d); oh = std::min(oh, o.out_h); ow = std::min(ow, o.out_w);
-            desc.out_d = od; desc.out_h = oh; desc.out_w = ow;
-        }
-        const bool f16 = f16_ok(parts, o.stride);
+        if (o.out_d) { desc.out_d = od; desc.out_h = oh; desc.out_w = ow; }
+        const bool f16 = s.w16;   // (a shape the f16x3 path refuses for another reason is pixie_conv3d_forward's to report)
         const bool raw = !o.pro && o.affine_store.empty();
         if (f16 && raw) for (auto& t : parts) stats(t);       // the input scale comes from the tensors' device-side |x|max
 
@@ -469,9 +470,8 @@ struct Exec {
             if (!dry) ok(pixie_conv3d_forward(&desc, stream), "pixie_conv3d_forward");
             return out;
         }
-        const bool sub = net->subpixel && o.upsample && ksize == 3 && o.stride == 1;   // unet.py: UNetRunner._conv
-        desc.d_w16 = w16(wkey, sub);
-        desc.w16_subpixel = sub ? 1 : 0;
+        desc.d_w16 = w16(wkey, s.subpixel);
+        desc.w16_subpixel = s.subpixel ? 1 : 0;
         if (o.skip_parts) {
             const std::vector<TP>& sp = *o.skip_parts;
             desc.d_skip_in0 = sp[0]->p; desc.skip_c0 = sp[0]->c;
@@ -479,7 +479,6 @@ struct Exec {
             desc.d_skip_w16 = w16(o.skip_key);
             desc.d_skip_bias = P(o.skip_key + ".bias");
             desc.d_skip_amax0 = sp[0]->slot; desc.d_skip_amax1 = sp.size() > 1 ? sp[1]->slot : nullptr;
-            if (dry) desc.d_skip_w16 = reinterpret_cast<const void*>(0x100);
         }
         if (raw) {
             desc.d_in_amax0 = parts[0]->slot;
@@ -487,18 +486,14 @@ struct Exec {
         } else {
             desc.in_bound = o.bound;
         }
-        // sizes of the optional buffers depend on the shape fields only; the dry run needs non-null placeholders for them
+        // the optional buffers are sized by the plan, which depends on the shape fields only: the dry run takes the same route
         std::unique_ptr<Scratch> workspace;
-        if (dry) { desc.d_w16 = reinterpret_cast<const void*>(0x100); }
-        if (net->split_k) {
-            const int64_t wsb = pixie_conv_workspace_bytes(&desc);
-            if (wsb > 0) { workspace.reset(new Scratch(this, wsb)); desc.d_workspace = workspace->as<void>(); if (dry) desc.d_workspace = reinterpret_cast<void*>(0x100); }
-        }
+        if (plan.workspace_bytes > 0) { workspace.reset(new Scratch(this, plan.workspace_bytes)); desc.d_workspace = workspace->as<void>(); }
         bool have_stats = false;
         if (net->fuse_stats) {
             // the output's channel sums and |x|max come out of the conv epilogue: no separate pass over the tensor
             uint32_t* slot = new_slot();
-            const int64_t nfl = pixie_conv_stats_floats(&desc);
+            const int64_t nfl = plan.stats_floats;
             if (nfl > 0 && (!workspace || net->split_stats)) {   // (split-K layers too: their reduce takes the statistics)
                 out->partials_off = arena.alloc(nfl * (int64_t)sizeof(float));
                 desc.d_out_stats = arena.ptr<float>(out->partials_off);
@@ -527,7 +522,7 @@ struct Exec {
         TP skip = parts[0];
         ConvOpt o2; o2.pro = &pro2; o2.affine_store = p + ".out_layers.0"; o2.act = ACT_LEAKY; o2.bound = norm_bound(p + ".out_layers.0", spatial);
         if (b.cin != b.cout) {
-            if (net->fold_skip && f16_ok({h}, 1) && f16_ok(parts, 1) && skip_foldable(h, b.cout, 3, parts)) {
+            if (net->fold_skip && skip_foldable(h, b.cout, 3, parts)) {
                 // out = conv(h) + skip_connection(x) in ONE launch: the 1x1x1 convolution rides in the accumulators of the second
                 // 3^3 convolution, the skip tensor never exists (conv3d_f16x3.hip, "folded skip")
                 skip.reset();

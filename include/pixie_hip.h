@@ -529,6 +529,62 @@ int pixie_raster_forward(const pixie_raster_desc* desc, int64_t* instances_out, 
 int pixie_sh_to_rgb(const float* d_shs, int64_t n, int k_coeffs, int degree, const float* d_pos /* [n][3] */, const float campos[3],
                     const float* d_rot /* [n_rot][9] or NULL */, int64_t n_rot, float* d_out /* [n][3] */, void* stream);
 
+/* A frame sequence in one call: `views` renders of the same n = n_dyn + n_static Gaussians at one image size.  Each view has its
+ * own camera (a host array of pixie_raster_view); width, height, bg and scale_modifier are shared (scale_modifier is carried for
+ * symmetry with pixie_raster_desc: the batch takes precomputed covariances only, which it does not scale).
+ * Geometry comes in two segments.  The dynamic one differs per view: d_means [views][n_dyn][3] and d_cov3d [views][n_dyn][6], view
+ * v starting means_view_stride / cov3d_view_stride ELEMENTS after view v - 1 (a slice of a larger (F, N, .) tensor needs no copy; 0
+ * shares one set among all views).  The static tail, d_static_means [n_static][3] and d_static_cov3d [n_static][6], is the same in
+ * every view and is indexed after the dynamic Gaussians (the unselected Gaussians of PG/gs_simulation.py:602-606 without the
+ * per-frame concatenation).  d_opacity is [n].  Exactly one colour source: d_colors ([n][3] per view, colors_view_stride elements
+ * apart, 0 = shared), or d_shs [n][k_coeffs][3] evaluated at sh_degree along normalise(mean - campos of the view) inside the
+ * projection kernel, as pixie_sh_to_rgb does without a rotation.
+ * Outputs, each NULL or given, at least one of the two images: d_out_color [views][3][height][width]; d_out_rgb8
+ * [views][height][width][3] = rintf(fminf(fmaxf(255 c, 0), 255)) of the same pixel; d_radii [views][n]; d_final_T and d_n_contrib
+ * [views][height][width].  d_workspace: 16-byte aligned, workspace_bytes >= pixie_raster_batch_workspace_bytes(n, views, width,
+ * height, max_instances); max_instances is the instance capacity one sort may use. */
+typedef struct pixie_raster_view {
+    float viewmatrix[16], projmatrix[16], campos[3];
+    float tanfovx, tanfovy;
+} pixie_raster_view;
+typedef struct pixie_raster_batch_desc {
+    int32_t views, n_dyn, n_static, width, height;
+    int32_t sh_degree, k_coeffs;       /* read with d_shs only */
+    float scale_modifier;
+    float bg[3];
+    int32_t pad_;
+    const pixie_raster_view* view;     /* HOST array [views] */
+    const float* d_means;              /* [views][n_dyn][3] */
+    const float* d_cov3d;              /* [views][n_dyn][6] */
+    int64_t means_view_stride, cov3d_view_stride;
+    const float* d_static_means;       /* [n_static][3] */
+    const float* d_static_cov3d;       /* [n_static][6] */
+    const float* d_opacity;            /* [n] */
+    const float* d_colors;             /* [views or 1][n][3], or NULL */
+    int64_t colors_view_stride;
+    const float* d_shs;                /* [n][k_coeffs][3], or NULL */
+    float* d_out_color;                /* or NULL */
+    uint8_t* d_out_rgb8;               /* or NULL */
+    int32_t* d_radii;                  /* or NULL */
+    float* d_final_T;                  /* or NULL */
+    int32_t* d_n_contrib;              /* or NULL */
+    void* d_workspace;
+    int64_t workspace_bytes;
+    int64_t max_instances;
+} pixie_raster_batch_desc;
+/* Bytes of workspace for a batch of `views` renders of n Gaussians: the part sized by views * n, plus the sort storage of the
+ * largest group of views, max_instances instances.  -1 on error. */
+int64_t pixie_raster_batch_workspace_bytes(int n, int views, int width, int height, int64_t max_instances);
+/* Projects all views * n Gaussian-views in one launch, scans their tile counts in one scan, synchronises `stream` ONCE to read the
+ * views + 1 offsets at the view boundaries (instances_out[v], where not NULL, is view v's instance count; a batch with n == 0
+ * synchronises never), then partitions the views greedily into groups of consecutive views whose instances fit max_instances
+ * (*groups_out, where not NULL) and -- asynchronously, per group -- duplicates with keys ((view in group * tiles + tile) << 32 |
+ * depth bits), sorts once, finds the (view, tile) ranges and renders on a (tiles_x, tiles_y, views in group) grid.  Within a
+ * (view, tile) run the instances are in (depth, index) order as in pixie_raster_forward, and the blend is the same code, so every
+ * image has the bits that call gives for that view.  If one view alone exceeds max_instances the call returns non-zero: d_radii and
+ * instances_out are written, no image output is touched, and pixie_last_error() names the view and the count it needs. */
+int pixie_raster_forward_batch(const pixie_raster_batch_desc* desc, int64_t* instances_out, int32_t* groups_out, void* stream);
+
 /* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)

@@ -100,6 +100,25 @@ class RasterDesc(C.Structure):
                 ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class RasterView(C.Structure):
+    """struct pixie_raster_view"""
+    _fields_ = [("viewmatrix", C.c_float * 16), ("projmatrix", C.c_float * 16), ("campos", C.c_float * 3),
+                ("tanfovx", C.c_float), ("tanfovy", C.c_float)]
+
+
+class RasterBatchDesc(C.Structure):
+    """struct pixie_raster_batch_desc"""
+    _fields_ = [("views", C.c_int32), ("n_dyn", C.c_int32), ("n_static", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("sh_degree", C.c_int32), ("k_coeffs", C.c_int32), ("scale_modifier", C.c_float), ("bg", C.c_float * 3), ("pad_", C.c_int32),
+                ("view", C.POINTER(RasterView)),
+                ("d_means", C.c_void_p), ("d_cov3d", C.c_void_p), ("means_view_stride", C.c_int64), ("cov3d_view_stride", C.c_int64),
+                ("d_static_means", C.c_void_p), ("d_static_cov3d", C.c_void_p), ("d_opacity", C.c_void_p),
+                ("d_colors", C.c_void_p), ("colors_view_stride", C.c_int64), ("d_shs", C.c_void_p),
+                ("d_out_color", C.c_void_p), ("d_out_rgb8", C.c_void_p), ("d_radii", C.c_void_p), ("d_final_T", C.c_void_p),
+                ("d_n_contrib", C.c_void_p),
+                ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("max_instances", C.c_int64)]
+
+
 # every symbol include/pixie_hip.h declares: name -> (restype, argtypes)
 _VP, _I, _I64, _D, _S = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_char_p
 _D3 = C.POINTER(C.c_double)
@@ -175,6 +194,8 @@ SIGNATURES = {
     "pixie_raster_workspace_bytes": (_I64, [_I, _I, _I, _I64]),
     "pixie_raster_forward": (_I, [C.POINTER(RasterDesc), C.POINTER(_I64), _VP]),
     "pixie_sh_to_rgb": (_I, [_VP, _I64, _I, _I, _VP, C.POINTER(C.c_float), _VP, _I64, _VP, _VP]),
+    "pixie_raster_batch_workspace_bytes": (_I64, [_I, _I, _I, _I, _I64]),
+    "pixie_raster_forward_batch": (_I, [C.POINTER(RasterBatchDesc), C.POINTER(_I64), C.POINTER(C.c_int32), _VP]),
     "pixie_field_to_particles": (_I, [C.POINTER(FieldDesc), _VP, _I, _I, _D, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 

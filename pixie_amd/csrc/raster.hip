@@ -13,14 +13,21 @@
 // them front to back for its pixel.  Every LDS read in that walk has one address for the whole wave (a broadcast), so what bounds
 // it is the wave's own instruction issue: per sample a ds_read_b64 and a ds_read_b128, ~28 VALU instructions up to the
 // contribution branch (expf's range handling included) and, inside that branch, a ds_read_b96 for the colour.
+//
+// pixie_raster_forward_batch renders `views` frames of one Gaussian set with the same chain run once over views * n Gaussian-views
+// (the raster_batch_* kernels): one projection launch, one scan, one synchronise that reads the views + 1 offsets at the view
+// boundaries, then per group of consecutive views (raster_batch_plan.h) one duplicate / sort / ranges / render with the view in the
+// key bits above the tile and in the render grid's z.  Same blend code, same order inside a (view, tile) run: same bits per image.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "raster_batch_plan.h"
 #include "raster_math.h"
 
 using namespace pixie;
@@ -217,6 +224,230 @@ int check_shape(const char* who, int n, int width, int height) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ a batch of views
+// Index conventions: a Gaussian-view is G = view * n + i over the whole batch (what preprocess and the scan see) and g = view in
+// group * n + i inside a sort group (the sorted value).  i < n_dyn is a dynamic Gaussian, the rest is the static tail.
+struct ViewCam {
+    rm::Camera cam;
+    float campos[3];
+    float pad_;
+};
+
+struct BatchGeom {
+    const float* means;                    // [views][n_dyn][3], view stride in elements
+    const float* cov3d;
+    int64_t means_stride, cov3d_stride;
+    const float* static_means;             // [n - n_dyn][3]
+    const float* static_cov3d;
+    int n, n_dyn;
+};
+
+// raster_preprocess_kernel over (Gaussian, view): blockIdx.y is the view, so the camera is wave-uniform.  With shs it also evaluates
+// the colour of every Gaussian that survives the projection, as sh_to_rgb_kernel does without a rotation.
+__global__ void __launch_bounds__(kBlock)
+raster_batch_preprocess_kernel(BatchGeom geo, int views, const ViewCam* __restrict__ cams, const float* __restrict__ opacity,
+                               const float* __restrict__ shs, int k_coeffs, int sh_degree, float* __restrict__ depth,
+                               float2* __restrict__ centre, float4* __restrict__ conic_opacity, int32_t* __restrict__ radii,
+                               float* __restrict__ rgb, uint64_t* __restrict__ tiles_touched) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const int v = blockIdx.y;
+    const int n = geo.n;
+    if (i > n) return;
+    if (i == n) {                                    // the scan runs over views * n + 1 counts
+        if (v == views - 1) tiles_touched[(size_t)views * n] = 0;
+        return;
+    }
+    const size_t G = (size_t)v * n + i;
+    const float* mp = i < geo.n_dyn ? geo.means + (size_t)v * geo.means_stride + (size_t)i * 3 : geo.static_means + (size_t)(i - geo.n_dyn) * 3;
+    const float* cp = i < geo.n_dyn ? geo.cov3d + (size_t)v * geo.cov3d_stride + (size_t)i * 6 : geo.static_cov3d + (size_t)(i - geo.n_dyn) * 6;
+    float p[3], c6[6];
+    for (int d = 0; d < 3; ++d) p[d] = mp[d];
+    for (int d = 0; d < 6; ++d) c6[d] = cp[d];
+    const ViewCam& vc = cams[v];
+    rm::Splat2D o;
+    if (!rm::project(p, c6, vc.cam, o)) {
+        radii[G] = 0;
+        tiles_touched[G] = 0;
+        return;
+    }
+    depth[G] = o.depth;
+    centre[G] = make_float2(o.px, o.py);
+    conic_opacity[G] = make_float4(o.ca, o.cb, o.cc, opacity[i]);
+    radii[G] = o.radius;
+    tiles_touched[G] = (uint64_t)((o.x1 - o.x0) * (o.y1 - o.y0));
+    if (shs) {
+        const float dx = p[0] - vc.campos[0], dy = p[1] - vc.campos[1], dz = p[2] - vc.campos[2];
+        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+        float c[3];
+        rm::sh_to_rgb(shs + (size_t)i * k_coeffs * 3, sh_degree, dx / len, dy / len, dz / len, c);
+        for (int d = 0; d < 3; ++d) rgb[G * 3 + d] = c[d];
+    }
+}
+
+// bounds[v] = offsets[v * n], v = 0 .. views: the instance offsets at the view boundaries, the only thing the host reads back
+__global__ void __launch_bounds__(kBlock)
+raster_batch_bounds_kernel(int views, int n, const uint64_t* __restrict__ offsets, uint64_t* __restrict__ bounds) {
+    const int v = blockIdx.x * kBlock + threadIdx.x;
+    if (v <= views) bounds[v] = offsets[(size_t)v * n];
+}
+
+// raster_duplicate_kernel for the views [v0, v0 + gridDim.y) of one group: keys carry (view in group * tiles + tile), values g
+__global__ void __launch_bounds__(kBlock)
+raster_batch_duplicate_kernel(int n, int v0, int tiles_x, int tiles_y, uint64_t group_base, uint64_t group_count,
+                              const float2* __restrict__ centre, const float* __restrict__ depth, const int32_t* __restrict__ radii,
+                              const uint64_t* __restrict__ offsets, uint64_t* __restrict__ keys, uint32_t* __restrict__ values) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int vg = blockIdx.y;
+    const size_t G = (size_t)(v0 + vg) * n + i;
+    const int r = radii[G];
+    if (r <= 0) return;
+    const float2 c = centre[G];
+    int x0, y0, x1, y1;
+    rm::tile_rect(c.x, c.y, r, tiles_x, tiles_y, x0, y0, x1, y1);
+    uint64_t off = offsets[G] - group_base;
+    uint64_t end = offsets[G + 1] - group_base;      // never written past: the rectangle is the one preprocess counted,
+    if (end > group_count) end = group_count;        // and never past what the host sized the group's buffers for
+    const uint64_t dbits = (uint64_t)__float_as_uint(depth[G]);
+    const uint32_t tile0 = (uint32_t)vg * (uint32_t)(tiles_x * tiles_y);
+    for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x) {
+            if (off >= end) return;
+            keys[off] = ((uint64_t)(tile0 + (uint32_t)(y * tiles_x + x)) << 32) | dbits;
+            values[off] = (uint32_t)((size_t)vg * n + i);
+            ++off;
+        }
+}
+
+// raster_render_kernel on a (tiles_x, tiles_y, views in group) grid: the same staging, the same blend loop and the same
+// compositing expression per view; the epilogue also writes the 8-bit frame where one is asked for.
+__global__ void __launch_bounds__(kBlock)
+raster_batch_render_kernel(int W, int H, int tiles_x, int tiles_y, int n, int v0, const uint2* __restrict__ ranges,
+                           const uint32_t* __restrict__ point_list, const float2* __restrict__ centre,
+                           const float4* __restrict__ conic_opacity, const float* __restrict__ colors, int64_t colors_stride, float bg0,
+                           float bg1, float bg2, float* __restrict__ out_color, uint8_t* __restrict__ out_rgb8,
+                           float* __restrict__ final_T, int32_t* __restrict__ n_contrib) {
+    __shared__ float2 s_xy[kBlock];
+    __shared__ float4 s_co[kBlock];
+    __shared__ float3 s_rgb[kBlock];
+    const int tid = threadIdx.x;
+    const int vg = blockIdx.z;
+    const size_t view = (size_t)(v0 + vg);
+    const int pix_x = blockIdx.x * rm::kTile + (tid & (rm::kTile - 1));
+    const int pix_y = blockIdx.y * rm::kTile + (tid >> 4);
+    const bool inside = pix_x < W && pix_y < H;
+    const float fx = (float)pix_x, fy = (float)pix_y;
+    const uint2 range = ranges[(size_t)vg * (tiles_x * tiles_y) + blockIdx.y * tiles_x + blockIdx.x];
+    int todo = (int)(range.y - range.x);
+    rm::PixelAcc acc = rm::pixel_start(!inside);
+    const size_t gbase = (size_t)v0 * n;                        // g -> G
+    const float* vcolors = colors + view * colors_stride;       // this view's [n][3]
+    const uint32_t g0 = (uint32_t)((size_t)vg * n);             // g -> i
+
+    for (uint32_t base = range.x; base < range.y; base += kBlock, todo -= kBlock) {
+        if (__syncthreads_count(acc.done) == kBlock) break;
+        if (base + tid < range.y) {
+            const uint32_t g = point_list[base + tid];
+            s_xy[tid] = centre[gbase + g];
+            s_co[tid] = conic_opacity[gbase + g];
+            const size_t ci = (size_t)(g - g0) * 3;
+            s_rgb[tid] = make_float3(vcolors[ci], vcolors[ci + 1], vcolors[ci + 2]);
+        }
+        __syncthreads();
+        const int cnt = todo < kBlock ? todo : kBlock;
+        for (int j = 0; !acc.done && j < cnt; ++j) {
+            const float2 xy = s_xy[j];
+            const float4 co = s_co[j];
+            const float3 rgb = s_rgb[j];
+            rm::blend(acc, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, fx, fy);
+        }
+    }
+    if (inside) {
+        const size_t pix = (size_t)pix_y * W + pix_x;
+        const size_t plane = (size_t)W * H;
+        const float r = acc.r + acc.T * bg0, g = acc.g + acc.T * bg1, b = acc.b + acc.T * bg2;
+        if (out_color) {
+            float* oc = out_color + view * 3 * plane;
+            oc[pix] = r;
+            oc[plane + pix] = g;
+            oc[2 * plane + pix] = b;
+        }
+        if (out_rgb8) {
+            uint8_t* o8 = out_rgb8 + (view * plane + pix) * 3;
+            o8[0] = (uint8_t)rintf(fminf(fmaxf(255.0f * r, 0.0f), 255.0f));
+            o8[1] = (uint8_t)rintf(fminf(fmaxf(255.0f * g, 0.0f), 255.0f));
+            o8[2] = (uint8_t)rintf(fminf(fmaxf(255.0f * b, 0.0f), 255.0f));
+        }
+        if (final_T) final_T[view * plane + pix] = acc.T;
+        if (n_contrib) n_contrib[view * plane + pix] = (int32_t)acc.last;
+    }
+}
+
+// Workspace of a batch: what the projection and the scan of views * n Gaussian-views need, then one group's sort storage.
+struct BatchLayout {
+    size_t cams, depth, centre, conic_opacity, radii, rgb, tiles_touched, offsets, bounds, ranges, scan_temp, scan_temp_bytes, fixed_bytes;
+    size_t keys_in, keys_out, vals_in, vals_out, sort_temp, total_bytes;
+    int max_group_views;
+};
+
+constexpr int kSortProbes = 16;
+
+// the sort's temporary storage for `m` instances of `group_views` views
+int sort_temp_bytes(size_t m, int64_t group_tiles, size_t& bytes) {
+    bytes = 0;
+    if (m == 0) return 0;
+    int bits = 0;
+    while ((1LL << bits) < group_tiles) ++bits;
+    PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                                    (uint32_t*)nullptr, m, 0, 32 + bits));
+    return 0;
+}
+
+int make_batch_layout(int n, int views, int tiles, int64_t instances, BatchLayout& L) {
+    const size_t total = (size_t)views * (size_t)n;
+    const int64_t by_key = (int64_t)UINT32_MAX / tiles;          // view in group * tiles + tile must fit 32 bits
+    L.max_group_views = (int)(by_key < views ? by_key : views);
+    size_t cur = 0;
+    L.cams = take(cur, sizeof(ViewCam) * (size_t)views);
+    L.depth = take(cur, sizeof(float) * total);
+    L.centre = take(cur, sizeof(float2) * total);
+    L.conic_opacity = take(cur, sizeof(float4) * total);
+    L.radii = take(cur, sizeof(int32_t) * total);
+    L.rgb = take(cur, sizeof(float) * 3 * total);
+    L.tiles_touched = take(cur, sizeof(uint64_t) * (total + 1));
+    L.offsets = take(cur, sizeof(uint64_t) * (total + 1));
+    L.bounds = take(cur, sizeof(uint64_t) * ((size_t)views + 1));
+    L.ranges = take(cur, sizeof(uint2) * (size_t)L.max_group_views * (size_t)tiles);
+    L.scan_temp_bytes = 0;
+    PX_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, L.scan_temp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(total + 1)));
+    L.scan_temp = take(cur, L.scan_temp_bytes);
+    L.fixed_bytes = cur;
+    const size_t m = (size_t)instances;
+    L.keys_in = take(cur, sizeof(uint64_t) * m);
+    L.keys_out = take(cur, sizeof(uint64_t) * m);
+    L.vals_in = take(cur, sizeof(uint32_t) * m);
+    L.vals_out = take(cur, sizeof(uint32_t) * m);
+    // A group may hold any count up to m, and the library's storage need not grow monotonically with the count: take the largest
+    // of a ladder of counts.  The call still checks each group's own need against what is left behind L.sort_temp.
+    size_t temp = 0;
+    for (int k = 1; k <= kSortProbes && m > 0; ++k) {
+        size_t b = 0;
+        if (sort_temp_bytes((m * k + kSortProbes - 1) / kSortProbes, (int64_t)L.max_group_views * tiles, b)) return 1;
+        if (b > temp) temp = b;
+    }
+    L.sort_temp = take(cur, temp);
+    L.total_bytes = cur;
+    return 0;
+}
+
+int check_batch_shape(const char* who, int n, int views, int width, int height, int64_t max_instances) {
+    if (check_shape(who, n, width, height)) return 1;
+    PX_REQUIRE(views >= 1 && views <= 65535, "%s: views %d outside 1..65535", who, views);
+    PX_REQUIRE((int64_t)views * n < (int64_t)INT_MAX, "%s: views %d x n %d exceeds one scan (2^31 - 1 counts)", who, views, n);
+    PX_REQUIRE(max_instances >= 0 && max_instances <= (int64_t)UINT32_MAX, "%s: max_instances %lld outside [0, 2^32)", who, (long long)max_instances);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,6 +547,142 @@ int pixie_sh_to_rgb(const float* d_shs, int64_t n, int k_coeffs, int degree, con
     hipLaunchKernelGGL(sh_to_rgb_kernel, dim3((unsigned)cdiv(n, kBlock)), dim3(kBlock), 0, as_stream(stream), d_shs, n, k_coeffs, degree, d_pos,
                        campos[0], campos[1], campos[2], d_rot, n_rot, d_out);
     PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int64_t pixie_raster_batch_workspace_bytes(int n, int views, int width, int height, int64_t max_instances) {
+    if (check_batch_shape("pixie_raster_batch_workspace_bytes", n, views, width, height, max_instances)) return -1;
+    const int tiles = cdiv(width, rm::kTile) * cdiv(height, rm::kTile);
+    BatchLayout L;
+    if (make_batch_layout(n, views, tiles, max_instances, L)) return -1;
+    return (int64_t)L.total_bytes;
+}
+
+int pixie_raster_forward_batch(const pixie_raster_batch_desc* d, int64_t* instances_out, int32_t* groups_out, void* stream) {
+    const char* who = "pixie_raster_forward_batch";
+    PX_REQUIRE(d, "%s: null descriptor", who);
+    if (groups_out) *groups_out = 0;
+    PX_REQUIRE(d->n_dyn >= 0 && d->n_static >= 0 && (int64_t)d->n_dyn + d->n_static < (int64_t)INT_MAX,
+               "%s: n_dyn %d, n_static %d must be >= 0 and sum below 2^31 - 1", who, d->n_dyn, d->n_static);
+    const int n = d->n_dyn + d->n_static, views = d->views;
+    if (check_batch_shape(who, n, views, d->width, d->height, d->max_instances)) return 1;
+    if (instances_out)
+        for (int v = 0; v < views; ++v) instances_out[v] = 0;
+    PX_REQUIRE(d->view, "%s: null pointer (view, the host array of per-view cameras, is required)", who);
+    for (int v = 0; v < views; ++v)
+        PX_REQUIRE(d->view[v].tanfovx > 0.0f && d->view[v].tanfovy > 0.0f, "%s: view %d: tanfovx %g, tanfovy %g must be positive", who, v,
+                   d->view[v].tanfovx, d->view[v].tanfovy);
+    PX_REQUIRE(d->d_out_color || d->d_out_rgb8, "%s: null pointer (one of d_out_color and d_out_rgb8 is required)", who);
+    if (n > 0) {
+        PX_REQUIRE(d->n_dyn == 0 || (d->d_means && d->d_cov3d), "%s: null pointer (d_means and d_cov3d are required for n_dyn %d)", who, d->n_dyn);
+        PX_REQUIRE(d->n_static == 0 || (d->d_static_means && d->d_static_cov3d),
+                   "%s: null pointer (d_static_means and d_static_cov3d are required for n_static %d)", who, d->n_static);
+        PX_REQUIRE(d->means_view_stride >= 0 && d->cov3d_view_stride >= 0 && d->colors_view_stride >= 0, "%s: negative view stride", who);
+        PX_REQUIRE(d->d_opacity, "%s: null pointer (d_opacity is required)", who);
+        PX_REQUIRE((d->d_colors != nullptr) != (d->d_shs != nullptr), "%s: give exactly one of d_colors and d_shs", who);
+        if (d->d_shs) {
+            PX_REQUIRE(d->sh_degree >= 0 && d->sh_degree <= 3, "%s: sh_degree %d outside 0..3", who, d->sh_degree);
+            PX_REQUIRE(d->k_coeffs >= (d->sh_degree + 1) * (d->sh_degree + 1), "%s: %d coefficients are fewer than degree %d needs", who,
+                       d->k_coeffs, d->sh_degree);
+        }
+    }
+    const int tiles_x = cdiv(d->width, rm::kTile), tiles_y = cdiv(d->height, rm::kTile), tiles = tiles_x * tiles_y;
+    BatchLayout L;
+    if (make_batch_layout(n, views, tiles, d->max_instances, L)) return 1;
+    PX_REQUIRE(d->d_workspace && d->workspace_bytes >= (int64_t)L.total_bytes,
+               "%s: workspace of %lld bytes is smaller than the %lld bytes that %d views of %d Gaussians, %d tiles and %lld instances need", who,
+               (long long)d->workspace_bytes, (long long)L.total_bytes, views, n, tiles, (long long)d->max_instances);
+    PX_REQUIRE(((uintptr_t)d->d_workspace & 15) == 0, "%s: d_workspace must be 16-byte aligned", who);
+    hipStream_t st = as_stream(stream);
+    char* ws = (char*)d->d_workspace;
+    const ViewCam* cams = (const ViewCam*)(ws + L.cams);
+    float* depth = (float*)(ws + L.depth);
+    float2* centre = (float2*)(ws + L.centre);
+    float4* conic_opacity = (float4*)(ws + L.conic_opacity);
+    int32_t* radii = d->d_radii ? d->d_radii : (int32_t*)(ws + L.radii);
+    float* rgb = (float*)(ws + L.rgb);
+    uint64_t* tiles_touched = (uint64_t*)(ws + L.tiles_touched);
+    uint64_t* offsets = (uint64_t*)(ws + L.offsets);
+    uint64_t* d_bounds = (uint64_t*)(ws + L.bounds);
+    uint2* ranges = (uint2*)(ws + L.ranges);
+
+    std::vector<uint64_t> bounds((size_t)views + 1, 0), counts((size_t)views, 0);
+    std::vector<ViewCam> host_cams;
+    if (n > 0) {
+        host_cams.resize((size_t)views);
+        for (int v = 0; v < views; ++v) {
+            const pixie_raster_view& pv = d->view[v];
+            host_cams[v].cam = rm::make_camera(pv.viewmatrix, pv.projmatrix, pv.tanfovx, pv.tanfovy, d->width, d->height);
+            for (int k = 0; k < 3; ++k) host_cams[v].campos[k] = pv.campos[k];
+            host_cams[v].pad_ = 0.0f;
+        }
+        // host_cams and bounds outlive both copies: the synchronise below comes before either goes out of scope
+        PX_CHECK_HIP(hipMemcpyAsync(ws + L.cams, host_cams.data(), sizeof(ViewCam) * (size_t)views, hipMemcpyHostToDevice, st));
+        BatchGeom geo;
+        geo.means = d->d_means; geo.cov3d = d->d_cov3d;
+        geo.means_stride = d->means_view_stride; geo.cov3d_stride = d->cov3d_view_stride;
+        geo.static_means = d->d_static_means; geo.static_cov3d = d->d_static_cov3d;
+        geo.n = n; geo.n_dyn = d->n_dyn;
+        hipLaunchKernelGGL(raster_batch_preprocess_kernel, dim3(cdiv((long)n + 1, kBlock), views), dim3(kBlock), 0, st, geo, views, cams,
+                           d->d_opacity, d->d_shs, d->k_coeffs, d->sh_degree, depth, centre, conic_opacity, radii, rgb, tiles_touched);
+        PX_CHECK_HIP(hipGetLastError());
+        size_t tb = L.scan_temp_bytes;
+        PX_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_temp, tb, (const uint64_t*)tiles_touched, offsets, (int)((size_t)views * n + 1), st));
+        hipLaunchKernelGGL(raster_batch_bounds_kernel, dim3(cdiv((long)views + 1, kBlock)), dim3(kBlock), 0, st, views, n, offsets, d_bounds);
+        PX_CHECK_HIP(hipGetLastError());
+        PX_CHECK_HIP(hipMemcpyAsync(bounds.data(), d_bounds, sizeof(uint64_t) * ((size_t)views + 1), hipMemcpyDeviceToHost, st));
+        PX_CHECK_HIP(hipStreamSynchronize(st));      // the only one of the call
+    }
+    for (int v = 0; v < views; ++v) {
+        counts[v] = bounds[v + 1] - bounds[v];
+        if (instances_out) instances_out[v] = (int64_t)counts[v];
+    }
+    std::vector<int32_t> begin((size_t)views + 1, 0);
+    const int64_t groups = rm::plan_groups(counts.data(), views, (uint64_t)d->max_instances, L.max_group_views, begin.data());
+    if (groups < 0) {
+        const int v = (int)(-1 - groups);
+        return set_error("%s: workspace too small: view %d alone has %llu instances, max_instances is %lld", who, v,
+                         (unsigned long long)counts[v], (long long)d->max_instances);
+    }
+    // every group's sort must find its temporary storage behind L.sort_temp before anything is rendered
+    const size_t temp_room = (size_t)d->workspace_bytes - L.sort_temp;
+    std::vector<size_t> temp_need((size_t)groups, 0);
+    for (int64_t k = 0; k < groups; ++k) {
+        const uint64_t count = bounds[begin[k + 1]] - bounds[begin[k]];
+        if (sort_temp_bytes((size_t)count, (int64_t)(begin[k + 1] - begin[k]) * tiles, temp_need[k])) return 1;
+        PX_REQUIRE(temp_need[k] <= temp_room, "%s: workspace too small: sorting the %llu instances of views %d..%d needs %llu bytes of temporary storage, %llu are left",
+                   who, (unsigned long long)count, begin[k], begin[k + 1] - 1, (unsigned long long)temp_need[k], (unsigned long long)temp_room);
+    }
+    if (groups_out) *groups_out = (int32_t)groups;
+
+    uint64_t* keys_in = (uint64_t*)(ws + L.keys_in);
+    uint64_t* keys_out = (uint64_t*)(ws + L.keys_out);
+    uint32_t* vals_in = (uint32_t*)(ws + L.vals_in);
+    uint32_t* sorted_vals = (uint32_t*)(ws + L.vals_out);
+    const float* colors = d->d_shs ? rgb : d->d_colors;
+    const int64_t colors_stride = d->d_shs ? (int64_t)n * 3 : d->colors_view_stride;
+    for (int64_t k = 0; k < groups; ++k) {
+        const int v0 = begin[k], gv = begin[k + 1] - begin[k];
+        const uint64_t count = bounds[v0 + gv] - bounds[v0];
+        const int64_t group_tiles = (int64_t)gv * tiles;
+        PX_CHECK_HIP(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)group_tiles, st));
+        if (count > 0) {
+            hipLaunchKernelGGL(raster_batch_duplicate_kernel, dim3(cdiv(n, kBlock), gv), dim3(kBlock), 0, st, n, v0, tiles_x, tiles_y, bounds[v0],
+                               count, centre, depth, radii, offsets, keys_in, vals_in);
+            PX_CHECK_HIP(hipGetLastError());
+            size_t tb = temp_need[k];
+            int bits = 0;
+            while ((1LL << bits) < group_tiles) ++bits;
+            PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.sort_temp, tb, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
+                                                            sorted_vals, (size_t)count, 0, 32 + bits, st));
+            hipLaunchKernelGGL(raster_ranges_kernel, dim3(cdiv((long)count, kBlock)), dim3(kBlock), 0, st, (int64_t)count, keys_out, ranges);
+            PX_CHECK_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(raster_batch_render_kernel, dim3(tiles_x, tiles_y, gv), dim3(kBlock), 0, st, d->width, d->height, tiles_x, tiles_y, n,
+                           v0, ranges, sorted_vals, centre, conic_opacity, colors, colors_stride, d->bg[0], d->bg[1], d->bg[2], d->d_out_color,
+                           d->d_out_rgb8, d->d_final_T, d->d_n_contrib);
+        PX_CHECK_HIP(hipGetLastError());
+    }
     return 0;
 }
 

@@ -5,7 +5,9 @@ Drop-ins for what that loop imports:
     signature, same two argument errors, (color (3, H, W), radii (N,)) back.  Forward only: nothing differentiates through a render
     in the simulation, and the outputs carry no graph.
   * `convert_SH` (utils/render_utils.py:113-130): one launch (pixie_sh_to_rgb) instead of the torch expression.
-And for `SceneBatch.run_frames` results: `render_frames`; for the frame files: `save_frame_png`.
+And for `SceneBatch.run_frames` results: `render_frames` (a call per frame) and `render_frame_batch` / `FrameBatchRasterizer` (the
+whole sequence in one pixie_raster_forward_batch call: one stream synchronise however many frames, the same bits per image); for
+the frame files: `save_frame_png`, `save_frame_pngs`.
 
 Differences from the reference, on purpose:
   * Gaussians with equal (tile, depth) are blended in index order (a stable sort), so an image is reproducible bit for bit;
@@ -16,6 +18,7 @@ There is no CPU compute path: a host tensor is refused.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import NamedTuple
 
 import torch
@@ -182,13 +185,18 @@ class GaussianRasterizer(torch.nn.Module):
         return (out, radii, final_T, n_contrib) if aux else (out, radii)
 
 
-def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=None, unselected=None, rasterizer=None):
+def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=None, unselected=None, rasterizer=None, batch=None):
     """Renders what `SceneBatch.run_frames` returns for a scene -- (pos (F, N, 3), cov (F, N, 6), ...) -- into (F, 3, H, W) on the
     device; frame f equals `GaussianRasterizer(settings_f)(pos[f], None, opacity, shs or colors_precomp, cov3D_precomp=cov[f])` bit
     for bit.  `settings_per_frame`: one GaussianRasterizationSettings, or one per frame (a moving camera) with one image size.
     Exactly one of `shs` (N', K, 3; evaluated per frame at sh_degree from campos) and `colors_precomp` (N', 3).
     `unselected`: (pos (M, 3), cov (M, 6)) of Gaussians that do not simulate, appended to every frame (gs_simulation.py:602-606);
-    `opacity` and the colours then cover N' = N + M Gaussians."""
+    `opacity` and the colours then cover N' = N + M Gaussians.
+    `batch`: None renders frame by frame (a call, a colour launch and a stream synchronise per frame); True or a
+    FrameBatchRasterizer hands the sequence to `render_frame_batch`, which gives the same images."""
+    if batch is not None and batch is not False:
+        return render_frame_batch(frames, settings_per_frame, opacity, shs=shs, colors_precomp=colors_precomp, unselected=unselected,
+                                  rasterizer=batch if isinstance(batch, FrameBatchRasterizer) else None)
     pos, cov = frames[0], frames[1]
     if cov is None:
         raise ValueError("render_frames: the frames carry no covariance (FrameSchedule.with_cov)")
@@ -217,6 +225,256 @@ def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=
     return out
 
 
+class FrameBatchOutput(NamedTuple):
+    color: object          # (V, 3, H, W) float32, or None
+    rgb8: object           # (V, H, W, 3) uint8, or None
+    radii: object          # (V, N) int32
+    final_T: object        # (V, H, W) float32, or None
+    n_contrib: object      # (V, H, W) int32, or None
+
+
+def _view_f32(t, what, n, tail):
+    """`t` as a float32 device tensor (V, n, tail) whose views are dense, and the view stride in elements.  A tensor that already is
+    one -- a slice of a larger (F, N, tail) tensor, or a view expanded with stride 0 -- is passed through without a copy."""
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise ValueError(f"{what} must be a tensor on a HIP device (there is no CPU path)")
+    t = t.detach()
+    if t.dim() != 3 or t.shape[1] != n or t.shape[2] != tail:
+        raise ValueError(f"{what} must be (views, {n}, {tail}), got {tuple(t.shape)}")
+    dense = t.dtype == torch.float32 and t.stride(0) >= 0 and (n <= 1 or t.stride(1) == tail) and t.stride(2) == 1
+    if not dense:
+        t = t.float().contiguous()
+    return t, int(t.stride(0))
+
+
+class FrameBatchRasterizer:
+    """Renders V views of one Gaussian set -- a frame sequence -- in one pixie_raster_forward_batch call: one projection launch, one
+    scan and one stream synchronise for the whole call, then one sort and one render launch per group of views.  The workspace is
+    kept between calls.  Its instance capacity starts at four tiles per Gaussian-view, as far as `max_workspace_bytes` allows, and
+    grows once when a single view needs more.  After a call `last_instances` holds the per-view instance counts and `last_groups`
+    the number of sort groups."""
+
+    def __init__(self, max_workspace_bytes=1 << 30):
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        self._workspace = None
+        self._capacity = 0
+        self._key = None
+        self._host = None              # (ids, settings kept alive, RasterView array, bg, scale_modifier, sh_degree, H, W)
+        self.last_instances = []
+        self.last_groups = 0
+
+    def _host_views(self, settings):
+        ids = tuple(id(s) for s in settings)
+        if self._host is not None and self._host[0] == ids:
+            return self._host
+        first = settings[0]
+        H, W = int(first.image_height), int(first.image_width)
+        unique = {}
+        for s in settings:
+            unique.setdefault(id(s), s)
+            if (int(s.image_height), int(s.image_width)) != (H, W):
+                raise ValueError("FrameBatchRasterizer: every view must have the same image size")
+            if float(s.scale_modifier) != float(first.scale_modifier) or int(s.sh_degree) != int(first.sh_degree):
+                raise ValueError("FrameBatchRasterizer: every view must have the same scale_modifier and sh_degree")
+        rows = []
+        for s in unique.values():
+            parts = []
+            for name, count in (("viewmatrix", 16), ("projmatrix", 16), ("campos", 3), ("bg", 3)):
+                v = torch.as_tensor(getattr(s, name)).detach().to(torch.float32).reshape(-1)
+                if v.numel() != count:
+                    raise ValueError(f"FrameBatchRasterizer: {name} must hold {count} values, got {v.numel()}")
+                parts.append(v)
+            if len({v.device for v in parts}) > 1:
+                parts = [v.cpu() for v in parts]
+            rows.append(torch.cat(parts))
+        if len({r.device for r in rows}) > 1:
+            rows = [r.cpu() for r in rows]
+        host = torch.stack(rows).cpu()                 # every distinct camera of the call in one device-to-host copy
+        row_of = {k: j for j, k in enumerate(unique)}
+        table = torch.empty((len(settings), 37), dtype=torch.float32)
+        for v, s in enumerate(settings):
+            r = host[row_of[id(s)]]
+            if not torch.equal(r[35:38], host[0, 35:38]):
+                raise ValueError("FrameBatchRasterizer: every view must have the same background")
+            table[v, :35] = r[:35]
+            table[v, 35], table[v, 36] = float(s.tanfovx), float(s.tanfovy)
+        views = (_lib.RasterView * len(settings)).from_buffer_copy(table.numpy().tobytes())
+        self._host = (ids, list(settings), views, [float(x) for x in host[0, 35:38]], float(first.scale_modifier), int(first.sh_degree), H, W)
+        return self._host
+
+    def _workspace_bytes(self, lib, n, views, W, H, capacity):
+        need = lib.pixie_raster_batch_workspace_bytes(n, views, W, H, int(capacity))
+        if need < 0:
+            _lib.check(1, "pixie_raster_batch_workspace_bytes", lib=lib)
+        return int(need)
+
+    def _ensure_workspace(self, lib, key, capacity, exact):
+        if self._workspace is not None and self._key == key and (self._capacity == capacity if exact else self._capacity >= capacity):
+            return
+        need = self._workspace_bytes(lib, key[0], key[1], key[2], key[3], capacity)
+        self._workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=key[4])
+        self._capacity, self._key = int(capacity), key
+
+    def _first_capacity(self, lib, n, views, W, H):
+        one = min(4 * n, 0xFFFFFFFF)
+        cap = min(one * views, 0xFFFFFFFF)
+        while cap > one and self._workspace_bytes(lib, n, views, W, H, cap) > self.max_workspace_bytes:
+            cap = max(cap // 2, one)
+        return cap
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    def forward(self, means, cov3D, settings, opacities, shs=None, colors_precomp=None, static=None, out=None, out_rgb8=None, aux=False,
+                capacity=None):
+        """means (V, N, 3) and cov3D (V, N, 6) on a HIP device (views dense, any view stride: a slice of a longer sequence is not
+        copied); `settings`: one GaussianRasterizationSettings or V of them with one image size, background, scale_modifier and
+        sh_degree; `static`: (pos (M, 3), cov (M, 6)) appended to every view; `opacities` (N + M,); exactly one of `shs`
+        (N + M, K, 3) and `colors_precomp` ((N + M, 3) shared, or (V, N + M, 3)).  `out`: a (V, 3, H, W) float32 tensor to fill, None
+        to allocate one, False for none; `out_rgb8`: a (V, H, W, 3) uint8 tensor, True to allocate one, None for none.
+        `capacity`: the instance capacity of one sort, instead of the rasteriser's own guess.  Returns a FrameBatchOutput."""
+        if (shs is None) == (colors_precomp is None):
+            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        if not torch.is_tensor(means) or not torch.is_tensor(cov3D) or means.dim() != 3:
+            raise ValueError("FrameBatchRasterizer: means3D and cov3D must be (views, N, 3) and (views, N, 6) tensors")
+        V, n_dyn = int(means.shape[0]), int(means.shape[1])
+        per_view = [settings] * V if isinstance(settings, GaussianRasterizationSettings) else list(settings)
+        if len(per_view) != V:
+            raise ValueError(f"FrameBatchRasterizer: {len(per_view)} settings for {V} views")
+        if V < 1:
+            raise ValueError("FrameBatchRasterizer: no view to render")
+        means, means_stride = _view_f32(means, "FrameBatchRasterizer: means3D", n_dyn, 3)
+        cov, cov_stride = _view_f32(cov3D, "FrameBatchRasterizer: cov3D", n_dyn, 6)
+        device = means.device
+        st_pos = st_cov = None
+        if static is not None:
+            st_pos = _device_f32(static[0], "FrameBatchRasterizer: static positions", (3,))
+            st_cov = _device_f32(static[1], "FrameBatchRasterizer: static covariances", (6,), st_pos.shape[0])
+        n_static = 0 if st_pos is None else int(st_pos.shape[0])
+        n = n_dyn + n_static
+        opac = _device_f32(opacities, "FrameBatchRasterizer: opacities", (), n)
+        sh = colors = None
+        colors_stride = 0
+        if shs is not None:
+            if not torch.is_tensor(shs) or shs.dim() != 3 or shs.shape[2] != 3:
+                raise ValueError(f"FrameBatchRasterizer: shs must be (N, K, 3), got {tuple(shs.shape) if torch.is_tensor(shs) else type(shs)}")
+            sh = _device_f32(shs, "FrameBatchRasterizer: shs", tuple(shs.shape[1:]), n)
+        elif torch.is_tensor(colors_precomp) and colors_precomp.dim() == 3:
+            if colors_precomp.shape[0] != V:
+                raise ValueError(f"FrameBatchRasterizer: per-view colors_precomp must be ({V}, {n}, 3), got {tuple(colors_precomp.shape)}")
+            colors, colors_stride = _view_f32(colors_precomp, "FrameBatchRasterizer: colors_precomp", n, 3)
+        else:
+            colors = _device_f32(colors_precomp, "FrameBatchRasterizer: colors_precomp", (3,), n)
+        _, _, views, bg, scale_modifier, sh_degree, H, W = self._host_views(per_view)
+
+        if out is None and (out_rgb8 is None or out_rgb8 is False):
+            out = True
+        if out is True:
+            out = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
+        elif out is None or out is False:
+            out = None
+        elif out.shape != (V, 3, H, W) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
+            raise ValueError(f"FrameBatchRasterizer: out must be a contiguous float32 ({V}, 3, {H}, {W}) tensor on {device}")
+        if out_rgb8 is True:
+            out_rgb8 = torch.empty((V, H, W, 3), dtype=torch.uint8, device=device)
+        elif out_rgb8 is None or out_rgb8 is False:
+            out_rgb8 = None
+        elif out_rgb8.shape != (V, H, W, 3) or out_rgb8.dtype != torch.uint8 or out_rgb8.device != device or not out_rgb8.is_contiguous():
+            raise ValueError(f"FrameBatchRasterizer: out_rgb8 must be a contiguous uint8 ({V}, {H}, {W}, 3) tensor on {device}")
+        radii = torch.empty((V, n), dtype=torch.int32, device=device)
+        final_T = torch.empty((V, H, W), dtype=torch.float32, device=device) if aux else None
+        n_contrib = torch.empty((V, H, W), dtype=torch.int32, device=device) if aux else None
+
+        lib = _lib.load()
+        d = _lib.RasterBatchDesc()
+        d.views, d.n_dyn, d.n_static, d.width, d.height = V, n_dyn, n_static, W, H
+        d.sh_degree, d.k_coeffs, d.scale_modifier = sh_degree, 0 if sh is None else int(sh.shape[1]), scale_modifier
+        d.bg = (C.c_float * 3)(*bg)
+        d.view = views
+        d.means_view_stride, d.cov3d_view_stride, d.colors_view_stride = means_stride, cov_stride, colors_stride
+        for name, t in (("d_means", means), ("d_cov3d", cov), ("d_static_means", st_pos), ("d_static_cov3d", st_cov), ("d_opacity", opac),
+                        ("d_colors", colors), ("d_shs", sh), ("d_out_color", out), ("d_out_rgb8", out_rgb8), ("d_radii", radii),
+                        ("d_final_T", final_T), ("d_n_contrib", n_contrib)):
+            setattr(d, name, t.data_ptr() if t is not None and t.numel() else None)
+        counts = (C.c_int64 * V)()
+        groups = C.c_int32(0)
+        key = (n, V, W, H, device)
+        with torch.cuda.device(device):
+            if capacity is not None:
+                self._ensure_workspace(lib, key, int(capacity), exact=True)
+            else:
+                self._ensure_workspace(lib, key, self._capacity if self._key == key else self._first_capacity(lib, n, V, W, H), exact=False)
+            for attempt in (0, 1):
+                d.d_workspace, d.workspace_bytes, d.max_instances = self._workspace.data_ptr(), self._workspace.numel(), self._capacity
+                rc = lib.pixie_raster_forward_batch(C.byref(d), counts, C.byref(groups), _lib.current_stream_ptr())
+                largest = max(counts)
+                if rc == 0 or attempt == 1 or largest <= self._capacity:
+                    break                                  # done, or the call failed for another reason: report it
+                self._ensure_workspace(lib, key, min(largest + largest // 2, 0xFFFFFFFF), exact=True)    # one view did not fit: grow once
+        _lib.check(rc, "pixie_raster_forward_batch", lib=lib)
+        self.last_instances = [int(c) for c in counts]
+        self.last_groups = int(groups.value)
+        return FrameBatchOutput(out, out_rgb8, radii, final_T, n_contrib)
+
+
+def _default_frames_per_call(n, n_frames, max_workspace_bytes):
+    """As many frames as keep the part of the workspace sized by views x N (60 bytes per Gaussian-view) within half of
+    `max_workspace_bytes`, and views x N within one scan."""
+    per_view = max(60 * n, 1)
+    fit = max(max_workspace_bytes // 2 // per_view, 1)
+    scan = max((2 ** 31 - 2) // max(n, 1), 1)
+    return int(max(1, min(n_frames, fit, scan, 65535)))
+
+
+def render_frame_batch(frames, settings_per_frame, opacity, shs=None, colors_precomp=None, unselected=None, frames_per_call=None, out=None,
+                       out_rgb8=None, rasterizer=None):
+    """`render_frames` through FrameBatchRasterizer: the frames `SceneBatch.run_frames` returns for a scene -- (pos (F, N, 3),
+    cov (F, N, 6), ...) -- go to the rasteriser as they lie on the device, `frames_per_call` at a time (default: what keeps the
+    workspace's fixed part within half of the rasteriser's `max_workspace_bytes`), with one stream synchronise per call instead of
+    one per frame, and without the per-frame concatenation of `unselected`.  Same arguments and argument errors as `render_frames`.
+    Returns (F, 3, H, W) float32, bit for bit what `render_frames` gives; `out` fills a given tensor.  `out_rgb8` (True, or a
+    (F, H, W, 3) uint8 tensor) also writes the 8-bit frames `save_frame_png` would; asked for alone, it is what is returned."""
+    pos, cov = frames[0], frames[1]
+    if cov is None:
+        raise ValueError("render_frame_batch: the frames carry no covariance (FrameSchedule.with_cov)")
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    n_frames = int(pos.shape[0])
+    per_frame = [settings_per_frame] * n_frames if isinstance(settings_per_frame, GaussianRasterizationSettings) else list(settings_per_frame)
+    if len(per_frame) != n_frames:
+        raise ValueError(f"render_frame_batch: {len(per_frame)} settings for {n_frames} frames")
+    if not torch.is_tensor(pos) or pos.device.type != "cuda":
+        raise ValueError("render_frame_batch: frames must be tensors on a HIP device (there is no CPU path)")
+    if n_frames == 0:
+        raise ValueError("render_frame_batch: no frame to render")
+    H, W = int(per_frame[0].image_height), int(per_frame[0].image_width)
+    only_rgb8 = out is None and out_rgb8 is not None and out_rgb8 is not False
+    if out is None and not only_rgb8:
+        out = torch.empty((n_frames, 3, H, W), dtype=torch.float32, device=pos.device)
+    if out_rgb8 is True:
+        out_rgb8 = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=pos.device)
+    elif out_rgb8 is False:
+        out_rgb8 = None
+    for t, shape, dtype in ((out, (n_frames, 3, H, W), torch.float32), (out_rgb8, (n_frames, H, W, 3), torch.uint8)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != pos.device or not t.is_contiguous()):
+            raise ValueError(f"render_frame_batch: an output must be a contiguous {dtype} {shape} tensor on {pos.device}")
+    r = rasterizer if rasterizer is not None else FrameBatchRasterizer()
+    n = int(pos.shape[1]) + (0 if unselected is None else int(unselected[0].shape[0]))
+    step = int(frames_per_call) if frames_per_call else _default_frames_per_call(n, n_frames, r.max_workspace_bytes)
+    if step < 1:
+        raise ValueError(f"render_frame_batch: frames_per_call {frames_per_call} must be positive")
+    per_view_colors = colors_precomp is not None and torch.is_tensor(colors_precomp) and colors_precomp.dim() == 3
+    instances, groups = [], 0
+    for f0 in range(0, n_frames, step):
+        f1 = min(f0 + step, n_frames)
+        r(pos[f0:f1], cov[f0:f1], per_frame[f0:f1], opacity, shs=shs, colors_precomp=colors_precomp[f0:f1] if per_view_colors else colors_precomp,
+          static=unselected, out=False if out is None else out[f0:f1], out_rgb8=None if out_rgb8 is None else out_rgb8[f0:f1])
+        instances += r.last_instances
+        groups += r.last_groups
+    r.last_instances, r.last_groups = instances, groups          # of the whole sequence
+    return out_rgb8 if only_rgb8 else out
+
+
 def save_frame_png(path, image):
     """Writes a (3, H, W) RGB image with values in [0, 1] as an 8-bit PNG: round(clip(255 x, 0, 255)), the file the reference's
     cvtColor + imwrite pair produces for frames/%05d.png.  Returns the path."""
@@ -229,3 +487,25 @@ def save_frame_png(path, image):
     a = (image.detach().float() * 255.0).clamp(0.0, 255.0).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
     Image.fromarray(a).save(path, format="PNG")
     return path
+
+
+def save_frame_pngs(dir, rgb8_or_images, start=0):
+    """Writes frames as `dir`/%05d.png from number `start`: a (F, H, W, 3) uint8 tensor as `render_frame_batch(out_rgb8=...)`
+    gives it, or (F, 3, H, W) float images, which are converted as `save_frame_png` converts one.  One device-to-host copy for the
+    whole sequence.  Returns the paths."""
+    t = rgb8_or_images
+    if not torch.is_tensor(t) or t.dim() != 4 or not ((t.dtype == torch.uint8 and t.shape[3] == 3) or (t.is_floating_point() and t.shape[1] == 3)):
+        raise ValueError("save_frame_pngs: frames must be a (F, H, W, 3) uint8 or a (F, 3, H, W) floating-point tensor")
+    try:
+        from PIL import Image
+    except ImportError as exc:
+        raise RuntimeError("save_frame_png needs Pillow (PIL), which is not installed") from exc
+    if t.dtype != torch.uint8:
+        t = (t.detach().float() * 255.0).clamp(0.0, 255.0).round().to(torch.uint8).permute(0, 2, 3, 1)
+    a = t.detach().contiguous().cpu().numpy()
+    os.makedirs(dir, exist_ok=True)
+    paths = []
+    for f in range(a.shape[0]):
+        paths.append(os.path.join(dir, "%05d.png" % (start + f)))
+        Image.fromarray(a[f]).save(paths[-1], format="PNG")
+    return paths

@@ -1,17 +1,24 @@
 #!/usr/bin/env python
 """Times the forward rasteriser at the frame-export sizes of DESIGN 3.8: a ball of N Gaussians (the synthetic MPM scene's sizes) at
 800 x 800.  HIP events around whole GaussianRasterizer calls (which include the one stream synchronise that reads the instance
-count); per-launch times come from running this script under `rocprofv3 --kernel-trace --stats`.  Prints one line per size."""
+count); per-launch times come from running this script under `rocprofv3 --kernel-trace --stats`.  Prints one line per size.
+
+`--frames F` times a frame sequence instead: F frames of the ball (it drifts and swells a little from frame to frame) rendered by
+`render_frames`, a call per frame, against one `render_frame_batch` call on the same tensors in the same process, the two
+alternating `--reps` times after `--warmup` rounds of both.  Host clock around each, ending in a device synchronise.  Prints the
+per-view instance counts, the group count, both times and whether the two image sequences are bit-equal."""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pixie_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer  # noqa: E402
+from pixie_amd.rasterizer import (FrameBatchRasterizer, GaussianRasterizationSettings, GaussianRasterizer, render_frame_batch,  # noqa: E402
+                                  render_frames)
 
 
 def look_at_camera(eye, target, fovx_deg, W, H, up, znear=0.01, zfar=100.0):
@@ -30,8 +37,36 @@ def look_at_camera(eye, target, fovx_deg, W, H, up, znear=0.01, zfar=100.0):
     return dict(V=V.astype(np.float32), P=(V @ Pm).astype(np.float32), tanfovx=float(tanx), tanfovy=float(tany), campos=eye.astype(np.float32))
 
 
+def time_frames(a, n, st, pos, cov, opacity, colors):
+    """F per-frame calls against one batched call on the same inputs; both rasterisers keep their workspace between rounds."""
+    F = a.frames
+    drift = torch.linspace(0.0, 0.05, F, device=pos.device)[:, None, None]
+    frames = ((pos[None] * (1.0 + drift)).contiguous(), (cov[None] * (1.0 + drift) ** 2).contiguous())
+    single, batch = GaussianRasterizer(st), FrameBatchRasterizer()
+    out_loop = out_batch = None
+    t_loop, t_batch = [], []
+    for rep in range(a.warmup + a.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out_loop = render_frames(frames, st, opacity, colors_precomp=colors, rasterizer=single)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        out_batch = render_frame_batch(frames, st, opacity, colors_precomp=colors, rasterizer=batch, out=out_batch)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if rep >= a.warmup:
+            t_loop.append((t1 - t0) * 1e3)
+            t_batch.append((t2 - t1) * 1e3)
+    med = lambda v: float(np.median(v))
+    print(json.dumps(dict(n=n, width=a.size, height=a.size, frames=F, reps=a.reps, per_frame_loop_ms=med(t_loop), batched_call_ms=med(t_batch),
+                          per_frame_loop_ms_min_max=[min(t_loop), max(t_loop)], batched_call_ms_min_max=[min(t_batch), max(t_batch)],
+                          batched_over_loop=med(t_batch) / med(t_loop), instances_per_view=batch.last_instances, groups=batch.last_groups,
+                          workspace_bytes=int(batch._workspace.numel()), bit_equal=bool(torch.equal(out_loop, out_batch)))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=0, help="time F per-frame calls against one batched call (0: the single-call timing)")
     ap.add_argument("--n", type=int, nargs="+", default=[100_000, 350_000])
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--reps", type=int, default=50)
@@ -53,6 +88,9 @@ def main():
         r = GaussianRasterizer(st)
         args = (t(pos), None, t(rng.uniform(0.2, 1.0, n).astype(np.float32)))
         kw = dict(colors_precomp=t(rng.uniform(0, 1, (n, 3)).astype(np.float32)), cov3D_precomp=t(cov))
+        if a.frames > 0:
+            time_frames(a, n, st, args[0], kw["cov3D_precomp"], args[2], kw["colors_precomp"])
+            continue
         for _ in range(a.warmup):
             img, radii, fT, nc = r(*args, aux=True, **kw)
         torch.cuda.synchronize()

@@ -586,6 +586,50 @@ int64_t pixie_raster_batch_workspace_bytes(int n, int views, int width, int heig
 int pixie_raster_forward_batch(const pixie_raster_batch_desc* desc, int64_t* instances_out, int32_t* groups_out, void* stream);
 
 /* ======================================================================================
+ * (E) Scene ingest -- PG/gs_simulation.py:403-438: everything between GaussianModel.load_ply and fill_particles.
+ * ====================================================================================== */
+/* d_block is the body of the checkpoint PLY as it lies in the file: [n][n_attr] float32, row-major, 16-byte aligned, n_attr <= 254.
+ * `columns` is a HOST table of 11 + 3 K entries, K = (sh_degree + 1)^2, naming the column of x, y, z, opacity, scale_0..2,
+ * rot_0..3, f_dc_0..2, f_rest_0..3(K-1)-1, in that order; every entry lies in [0, n_attr).  `rotations` holds n_rotations (<= 8)
+ * row-major 3x3 matrices applied in order (p @ R^T, R S R^T); sim_area = (x0, x1, y0, y1, z0, z1) on the rotated position, strict,
+ * read when has_sim_area.  A Gaussian is dropped unless sigmoid(opacity) > opacity_threshold, selected if inside sim_area (or there
+ * is none), unselected otherwise.
+ * Outputs, n rows of room each: selected Gaussians, in file order, fill rows [0, n_sel); unselected ones, in file order, rows
+ * [n_sel, n_sel + n_unsel).  d_pos [.][3]: selected = ((rotated - mean) * scale + 1) + (0, 0, z_shift), unselected = the file's
+ * x y z.  d_cov [.][6] (00 01 02 11 12 22): the covariance of exp(scale) and the normalised quaternion; selected rows rotated and
+ * times scale^2.  d_opacity [.][1]: sigmoid.  d_shs [.][K][3]: the file's f_dc | f_rest columns, (channel, coefficient) ->
+ * (coefficient, channel).  mean = (min + max) / 2 and scale = 1 / max(max - min) over the selected rotated positions, float32. */
+typedef struct pixie_ingest_desc {
+    int64_t n;
+    int32_t n_attr, sh_degree, n_rotations, has_sim_area;
+    float rotations[72];
+    float sim_area[6];
+    float opacity_threshold, z_shift;
+    const float* d_block;
+    const int32_t* columns;            /* HOST array [11 + 3 K] */
+    float* d_pos;
+    float* d_cov;
+    float* d_opacity;
+    float* d_shs;
+    void* d_workspace;
+    int64_t workspace_bytes;
+} pixie_ingest_desc;
+/* What pixie_scene_ingest returns besides 0 and 1 (any other error): each leaves pixie_last_error() set and the outputs unwritten. */
+enum {
+    PIXIE_INGEST_NO_SELECTION = 2,       /* no Gaussian passes the opacity filter inside sim_area */
+    PIXIE_INGEST_ZERO_EXTENT = 3,        /* max(max - min) == 0, one selected Gaussian included: 1 / 0 is no scale */
+    PIXIE_INGEST_TOO_MANY_ROTATIONS = 4, /* n_rotations > 8 */
+    PIXIE_INGEST_TOO_MANY_ROWS = 5       /* n > 2^31 - 2 */
+};
+/* Bytes of 16-byte aligned device workspace for n Gaussians (two 8-byte words per Gaussian and the scan's storage).  -1 on error. */
+int64_t pixie_scene_ingest_workspace_bytes(int64_t n);
+/* Classifies every Gaussian, bounds the selected ones, scans, synchronises `stream` ONCE to read counts_out (selected, unselected,
+ * dropped), scale_out and mean_out (each NULL or given), then -- asynchronously, in one launch -- writes the four outputs.  On
+ * PIXIE_INGEST_NO_SELECTION and PIXIE_INGEST_ZERO_EXTENT the counts are written and nothing is launched after the synchronise.
+ * Deterministic: the same input gives the same bits. */
+int pixie_scene_ingest(const pixie_ingest_desc* desc, int64_t counts_out[3], float scale_out[1], float mean_out[3], void* stream);
+
+/* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)
  * load; the production library libpixie_hip.so exports none of them and carries no trace buffer.

@@ -119,6 +119,19 @@ class RasterBatchDesc(C.Structure):
                 ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("max_instances", C.c_int64)]
 
 
+class IngestDesc(C.Structure):
+    """struct pixie_ingest_desc"""
+    _fields_ = [("n", C.c_int64), ("n_attr", C.c_int32), ("sh_degree", C.c_int32), ("n_rotations", C.c_int32), ("has_sim_area", C.c_int32),
+                ("rotations", C.c_float * 72), ("sim_area", C.c_float * 6), ("opacity_threshold", C.c_float), ("z_shift", C.c_float),
+                ("d_block", C.c_void_p), ("columns", C.POINTER(C.c_int32)),
+                ("d_pos", C.c_void_p), ("d_cov", C.c_void_p), ("d_opacity", C.c_void_p), ("d_shs", C.c_void_p),
+                ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+# pixie_scene_ingest's return codes besides 0 and 1 (include/pixie_hip.h)
+INGEST_NO_SELECTION, INGEST_ZERO_EXTENT, INGEST_TOO_MANY_ROTATIONS, INGEST_TOO_MANY_ROWS = 2, 3, 4, 5
+
+
 # every symbol include/pixie_hip.h declares: name -> (restype, argtypes)
 _VP, _I, _I64, _D, _S = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_char_p
 _D3 = C.POINTER(C.c_double)
@@ -196,6 +209,8 @@ SIGNATURES = {
     "pixie_sh_to_rgb": (_I, [_VP, _I64, _I, _I, _VP, C.POINTER(C.c_float), _VP, _I64, _VP, _VP]),
     "pixie_raster_batch_workspace_bytes": (_I64, [_I, _I, _I, _I, _I64]),
     "pixie_raster_forward_batch": (_I, [C.POINTER(RasterBatchDesc), C.POINTER(_I64), C.POINTER(C.c_int32), _VP]),
+    "pixie_scene_ingest_workspace_bytes": (_I64, [_I64]),
+    "pixie_scene_ingest": (_I, [C.POINTER(IngestDesc), C.POINTER(_I64), C.POINTER(C.c_float), C.POINTER(C.c_float), _VP]),
     "pixie_field_to_particles": (_I, [C.POINTER(FieldDesc), _VP, _I, _I, _D, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 

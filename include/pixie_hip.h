@@ -586,6 +586,49 @@ int64_t pixie_raster_batch_workspace_bytes(int n, int views, int width, int heig
 int pixie_raster_forward_batch(const pixie_raster_batch_desc* desc, int64_t* instances_out, int32_t* groups_out, void* stream);
 
 /* ======================================================================================
+ * (D') Backward pass of the rasteriser: the gradient of one pixie_raster_forward render with respect to its inputs.
+ * ====================================================================================== */
+/* The gradient is the exact derivative of the forward as section (D) defines it, with every discrete decision held fixed: culling,
+ * radius, tile rectangle, order, the power > 0 / 1/255 / 1e-4 rules, and min(0.99, .), the 1.3 tanfov clamp of the projection and the
+ * max(., 0) of the colour each taking the branch they took.  Camera matrices get no gradient.
+ * `forward` is the descriptor of the forward call as it was passed, with d_final_T and d_n_contrib given, its outputs (d_out_color,
+ * d_radii, d_n_contrib) as that call wrote them and its workspace untouched since; `instances` is the count that call returned.
+ * With d_shs ([n][sh_k][3]) the colours forward.d_colors are taken to be pixie_sh_to_rgb(d_shs, sh_degree, d_means, campos) without
+ * a rotation, and the colour gradient is carried on to d_dL_dshs and, through the view direction, to d_dL_dmeans3D.
+ * d_dL_dcolor is [3][height][width].  Outputs, each NULL (not computed) or given: d_dL_dmeans3D [n][3]; d_dL_dmeans2D [n][3] =
+ * (dL/dpx 0.5 width, dL/dpy 0.5 height, 0) for the pixel centre (px, py), the convention of diff_gaussian_rasterization;
+ * d_dL_dopacity [n]; d_dL_dcolors [n][3]; d_dL_dshs [n][sh_k][3] (needs d_shs); d_dL_dcov3D [n][6], one value per upper-triangle
+ * entry, when the forward took d_cov3d, or d_dL_dscales [n][3] and d_dL_drotations [n][4] when it took the pair.  Culled Gaussians
+ * (radius 0) get exact zeros.  d_grad_workspace: 16-byte aligned, grad_workspace_bytes >= pixie_raster_backward_workspace_bytes. */
+typedef struct pixie_raster_backward_desc {
+    pixie_raster_desc forward;
+    int64_t instances;
+    const float* d_shs;                /* [n][sh_k][3], or NULL */
+    int32_t sh_k, sh_degree;           /* read with d_shs only */
+    float campos[3];                   /* read with d_shs only */
+    int32_t pad_;
+    const float* d_dL_dcolor;          /* [3][height][width] */
+    float* d_dL_dmeans3D;
+    float* d_dL_dmeans2D;
+    float* d_dL_dopacity;
+    float* d_dL_dcolors;
+    float* d_dL_dshs;
+    float* d_dL_dcov3D;
+    float* d_dL_dscales;
+    float* d_dL_drotations;
+    void* d_grad_workspace;
+    int64_t grad_workspace_bytes;
+} pixie_raster_backward_desc;
+/* Bytes of the gradient workspace: nine floats per instance (one slot per Gaussian and tile of its rectangle).  -1 on error. */
+int64_t pixie_raster_backward_workspace_bytes(int n, int width, int height, int64_t instances);
+/* Asynchronous on `stream`, no synchronise.  Zeroes the per-instance buffer, walks every tile front to back up to its largest
+ * n_contrib, reducing each Gaussian's nine partials (centre 2, conic 3, opacity 1, colour 3) over the tile in a fixed order into its
+ * slot, then sums each Gaussian's slots sequentially and applies the per-Gaussian chain.  No floating-point atomics: the gradients
+ * are bit-identical from run to run.  n == 0 or zero instances zeroes the outputs and launches nothing else; with every output NULL
+ * the call checks its arguments and does nothing. */
+int pixie_raster_backward(const pixie_raster_backward_desc* desc, void* stream);
+
+/* ======================================================================================
  * (E) Scene ingest -- PG/gs_simulation.py:403-438: everything between GaussianModel.load_ply and fill_particles.
  * ====================================================================================== */
 /* d_block is the body of the checkpoint PLY as it lies in the file: [n][n_attr] float32, row-major, 16-byte aligned, n_attr <= 254.

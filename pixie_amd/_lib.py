@@ -100,6 +100,16 @@ class RasterDesc(C.Structure):
                 ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class RasterBackwardDesc(C.Structure):
+    """struct pixie_raster_backward_desc"""
+    _fields_ = [("forward", RasterDesc), ("instances", C.c_int64),
+                ("d_shs", C.c_void_p), ("sh_k", C.c_int32), ("sh_degree", C.c_int32), ("campos", C.c_float * 3), ("pad_", C.c_int32),
+                ("d_dL_dcolor", C.c_void_p),
+                ("d_dL_dmeans3D", C.c_void_p), ("d_dL_dmeans2D", C.c_void_p), ("d_dL_dopacity", C.c_void_p), ("d_dL_dcolors", C.c_void_p),
+                ("d_dL_dshs", C.c_void_p), ("d_dL_dcov3D", C.c_void_p), ("d_dL_dscales", C.c_void_p), ("d_dL_drotations", C.c_void_p),
+                ("d_grad_workspace", C.c_void_p), ("grad_workspace_bytes", C.c_int64)]
+
+
 class RasterView(C.Structure):
     """struct pixie_raster_view"""
     _fields_ = [("viewmatrix", C.c_float * 16), ("projmatrix", C.c_float * 16), ("campos", C.c_float * 3),
@@ -206,6 +216,8 @@ SIGNATURES = {
     "pixie_dbscan_roots": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, C.POINTER(_D), _D, _D, _I, _VP, _VP, _VP, _VP]),
     "pixie_raster_workspace_bytes": (_I64, [_I, _I, _I, _I64]),
     "pixie_raster_forward": (_I, [C.POINTER(RasterDesc), C.POINTER(_I64), _VP]),
+    "pixie_raster_backward_workspace_bytes": (_I64, [_I, _I, _I, _I64]),
+    "pixie_raster_backward": (_I, [C.POINTER(RasterBackwardDesc), _VP]),
     "pixie_sh_to_rgb": (_I, [_VP, _I64, _I, _I, _VP, C.POINTER(C.c_float), _VP, _I64, _VP, _VP]),
     "pixie_raster_batch_workspace_bytes": (_I64, [_I, _I, _I, _I, _I64]),
     "pixie_raster_forward_batch": (_I, [C.POINTER(RasterBatchDesc), C.POINTER(_I64), C.POINTER(C.c_int32), _VP]),

@@ -17,7 +17,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpixie_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpixie_hip_diag.so")   # same sources + -DPIXIE_DIAG (tests, profilers)
 ARCH = "gfx950"
-SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "scene_ingest.hip"]
+SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
 # Per-file flags.  mpm.hip: hipcc's SLP vectoriser turns a third of the fused MPM kernel's fp32 arithmetic into packed
@@ -29,9 +29,12 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 # (-ffp-contract=off there too) and as a float32 NumPy evaluation does: what is left between the kernels and that evaluation is
 # the device's expf alone, and the scales / rotations route is bit-equal to the cov3D route fed with the helper's covariances
 # (tests/test_raster_hip.py).  The price, a mul + add where an fma would do (about four per sample in the render loop), is unmeasured.
+# raster_backward.hip: the same, for raster_grad_math.h and tests/test_raster_grad_math.py; its walk also repeats the forward's blend
+# operation for operation, which only an unfused build does with the forward's bits.
 # scene_ingest.hip: the same, for ingest_math.h and tests/test_scene_ingest_math.py; the kernels move ~480 bytes per Gaussian, so
 # the unfused arithmetic is not what bounds them.
-EXTRA_FLAGS = {"mpm.hip": ["-fno-slp-vectorize"], "raster.hip": ["-ffp-contract=off"], "scene_ingest.hip": ["-ffp-contract=off"]}
+EXTRA_FLAGS = {"mpm.hip": ["-fno-slp-vectorize"], "raster.hip": ["-ffp-contract=off"], "raster_backward.hip": ["-ffp-contract=off"],
+               "scene_ingest.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -1,17 +1,27 @@
-"""Forward 3D Gaussian splatting rasteriser: the per-frame render of gs_simulation.py's frame loop (:590, :610-619, :630-631).
+"""3D Gaussian splatting rasteriser: the per-frame render of gs_simulation.py's frame loop (:590, :610-619, :630-631), and, through
+torch autograd, the differentiable render that gaussian-splatting/train.py optimises through.
 
 Drop-ins for what that loop imports:
   * `GaussianRasterizationSettings`, `GaussianRasterizer` (diff_gaussian_rasterization/__init__.py:157-220): same fields, same call
-    signature, same two argument errors, (color (3, H, W), radii (N,)) back.  Forward only: nothing differentiates through a render
-    in the simulation, and the outputs carry no graph.
+    signature, same two argument errors, (color (3, H, W), radii (N,)) back.  With grad mode on and an input that requires grad the
+    colour carries a graph whose backward is one pixie_raster_backward call (HIP, include/pixie_hip.h section D'); otherwise, and
+    always under torch.no_grad() or with `out=` given, the render is the forward-only one of the simulation loop, bit for bit.
   * `convert_SH` (utils/render_utils.py:113-130): one launch (pixie_sh_to_rgb) instead of the torch expression.
 And for `SceneBatch.run_frames` results: `render_frames` (a call per frame) and `render_frame_batch` / `FrameBatchRasterizer` (the
 whole sequence in one pixie_raster_forward_batch call: one stream synchronise however many frames, the same bits per image); for
 the frame files: `save_frame_png`, `save_frame_pngs`.
 
+What is differentiable: `GaussianRasterizer.forward` with respect to means3D, means2D, opacities, shs or colors_precomp, and scales and
+rotations or cov3D_precomp.  What is not: `render_frames`, `render_frame_batch` and `FrameBatchRasterizer` stay forward-only; double
+backward is not supported; the camera matrices, campos and bg get no gradient; final_T (aux=True) carries none.
+
 Differences from the reference, on purpose:
-  * Gaussians with equal (tile, depth) are blended in index order (a stable sort), so an image is reproducible bit for bit;
-  * `means2D` is ignored (upstream it only carries a gradient);
+  * Gaussians with equal (tile, depth) are blended in index order (a stable sort), so an image is reproducible bit for bit, and so
+    are the gradients: the backward reduces in a fixed order and uses no floating-point atomics;
+  * the gradient is the exact derivative of the forward with every discrete decision held fixed, which differs from upstream's
+    backward.cu in three small places: no gradient through an active min(0.99, .), the Jacobian term under an active 1.3 tanfov
+    clamp is differentiated as the forward computes it, and no 1e-7 is added to the determinant's square;
+  * the values of `means2D` are ignored (as upstream, it only receives a gradient: (dL/dpx 0.5 W, dL/dpy 0.5 H, 0));
   * `prefiltered` and `debug` are accepted and unused.
 There is no CPU compute path: a host tensor is refused.
 """
@@ -91,10 +101,99 @@ def convert_SH(shs_view, viewpoint_camera, pc, position, rotation=None):
     return sh_to_rgb(shs_view, int(pc.active_sh_degree), position, viewpoint_camera.camera_center, rotation)
 
 
+class _OwnedWorkspace:
+    """The workspace of one differentiable render: it belongs to that render's autograd node, because the backward reads it as the
+    forward left it and the module's shared workspace is overwritten by the next call."""
+
+    def __init__(self):
+        self._workspace = None
+        self._capacity = 0
+        self._key = None
+
+
+def _ensure_workspace(holder, lib, n, W, H, device, instances):
+    key = (n, W, H, device)
+    if holder._workspace is not None and holder._key == key and holder._capacity >= instances:
+        return
+    need = lib.pixie_raster_workspace_bytes(n, W, H, int(instances))
+    if need < 0:
+        _lib.check(1, "pixie_raster_workspace_bytes", lib=lib)
+    holder._workspace = torch.empty((max(int(need), 16),), dtype=torch.uint8, device=device)
+    holder._capacity, holder._key = int(instances), key
+
+
+_GRAD_INPUTS = ("means3D", "means2D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
+
+
+class _Rasterize(torch.autograd.Function):
+    """The differentiable render: forward = GaussianRasterizer._render on a workspace of its own, backward = one pixie_raster_backward
+    call on the current stream.  Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, rasterizer, aux, *inputs):
+        given = dict(zip(_GRAD_INPUTS, inputs))
+        holder = _OwnedWorkspace()
+        out, radii, final_T, n_contrib, state = rasterizer._render(holder, given["means3D"], given["opacities"], given["shs"],
+                                                                   given["colors_precomp"], given["scales"], given["rotations"],
+                                                                   given["cov3D_precomp"], None, True)
+        ctx.state = state                      # descriptor, workspace, instance count, SH parameters
+        ctx.meta = [None if t is None else (tuple(t.shape), t.dtype) for t in inputs]
+        ctx.save_for_backward(out, radii, final_T, n_contrib, *state["tensors"])
+        ctx.mark_non_differentiable(radii, final_T, n_contrib)
+        return out, radii, final_T, n_contrib
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_radii, g_final_T, g_n_contrib):
+        none = (None,) * (2 + len(_GRAD_INPUTS))
+        if g_out is None:
+            return none
+        st = ctx.state
+        saved = ctx.saved_tensors              # raises if one of them was modified in place since the forward
+        out = saved[0]
+        device, n = out.device, st["n"]
+        need = dict(zip(_GRAD_INPUTS, ctx.needs_input_grad[2:]))
+        shapes = {"means3D": (n, 3), "means2D": (n, 3), "opacities": (n,), "shs": (n, st["sh_k"], 3), "colors_precomp": (n, 3),
+                  "scales": (n, 3), "rotations": (n, 4), "cov3D_precomp": (n, 6)}
+        grads = {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in _GRAD_INPUTS if need[k]}
+        g_out = g_out.detach().to(torch.float32).contiguous()
+        lib = _lib.load()
+        b = _lib.RasterBackwardDesc()
+        b.forward = st["desc"]
+        b.instances = st["instances"]
+        if st["shs"] is not None:
+            b.d_shs, b.sh_k, b.sh_degree = _ptr(st["shs"]), st["sh_k"], st["sh_degree"]
+            b.campos = (C.c_float * 3)(*st["campos"])
+        b.d_dL_dcolor = g_out.data_ptr()
+        for field, key in (("d_dL_dmeans3D", "means3D"), ("d_dL_dmeans2D", "means2D"), ("d_dL_dopacity", "opacities"), ("d_dL_dshs", "shs"),
+                           ("d_dL_dcolors", "colors_precomp"), ("d_dL_dscales", "scales"), ("d_dL_drotations", "rotations"),
+                           ("d_dL_dcov3D", "cov3D_precomp")):
+            setattr(b, field, _ptr(grads.get(key)))
+        with torch.cuda.device(device):
+            nb = lib.pixie_raster_backward_workspace_bytes(n, st["W"], st["H"], st["instances"])
+            if nb < 0:
+                _lib.check(1, "pixie_raster_backward_workspace_bytes", lib=lib)
+            gws = torch.empty((max(int(nb), 16),), dtype=torch.uint8, device=device)
+            b.d_grad_workspace, b.grad_workspace_bytes = gws.data_ptr(), gws.numel()
+            rc = lib.pixie_raster_backward(C.byref(b), _lib.current_stream_ptr())
+        _lib.check(rc, "pixie_raster_backward", lib=lib)
+        result = []
+        for k, meta in zip(_GRAD_INPUTS, ctx.meta):
+            g = grads.get(k)
+            result.append(None if g is None or meta is None else g.reshape(meta[0]).to(meta[1]))
+        return (None, None) + tuple(result)
+
+
 class GaussianRasterizer(torch.nn.Module):
     """`GaussianRasterizer(raster_settings)(means3D, means2D, opacities, ...)` -> (color (3, H, W), radii (N,) int32).
     The workspace is kept between calls and grows when a render needs more instances (Gaussian-tile pairs) than it holds.
-    After a call, `last_instances` is that render's instance count; `forward(..., aux=True)` also returns (final_T, n_contrib)."""
+    After a call, `last_instances` is that render's instance count; `forward(..., aux=True)` also returns (final_T, n_contrib).
+
+    With grad mode on, an input among means3D, means2D, opacities, shs / colors_precomp, scales / rotations / cov3D_precomp that requires
+    grad, and no `out=`, the colour is differentiable with respect to those inputs (radii, final_T and n_contrib are not; neither are
+    the camera matrices; double backward is not supported).  Such a render runs on a workspace owned by its autograd node, so any
+    number of renders may be outstanding before their backwards run, in any order.  Otherwise the call is the forward-only render:
+    same workspace reuse, same launches, same bits as before."""
 
     def __init__(self, raster_settings):
         super().__init__()
@@ -104,17 +203,11 @@ class GaussianRasterizer(torch.nn.Module):
         self._key = None
         self._host = None              # (settings object, viewmatrix, projmatrix, bg as ctypes arrays): read back once per settings
         self.last_instances = 0
+        self._owned_hint = (None, 0)   # (shape key, instance capacity) of the last differentiable render
 
     def _ensure_workspace(self, lib, n, device, instances):
         s = self.raster_settings
-        key = (n, int(s.image_width), int(s.image_height), device)
-        if self._workspace is not None and self._key == key and self._capacity >= instances:
-            return
-        need = lib.pixie_raster_workspace_bytes(n, key[1], key[2], int(instances))
-        if need < 0:
-            _lib.check(1, "pixie_raster_workspace_bytes", lib=lib)
-        self._workspace = torch.empty((max(int(need), 16),), dtype=torch.uint8, device=device)
-        self._capacity, self._key = int(instances), key
+        _ensure_workspace(self, lib, n, int(s.image_width), int(s.image_height), device, instances)
 
     def _host_settings(self):
         s = self.raster_settings
@@ -133,10 +226,24 @@ class GaussianRasterizer(torch.nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        inputs = (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if out is None and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in inputs):
+            color, radii, final_T, n_contrib = _Rasterize.apply(self, aux, *inputs)
+            return (color, radii, final_T, n_contrib) if aux else (color, radii)
+        res = self._render(self, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux)
+        return res[:4] if aux else res[:2]
+
+    def _render(self, holder, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux):
+        """One pixie_raster_forward on `holder`'s workspace (the module itself, or the _OwnedWorkspace of a differentiable render).
+        Returns (out, radii, final_T, n_contrib, what a backward needs)."""
+        s = self.raster_settings
         means = _device_f32(means3D, "GaussianRasterizer: means3D", (3,))
         n, device = means.shape[0], means.device
+        sh = None
         if shs is not None:
             colors = sh_to_rgb(shs, int(s.sh_degree), means, self._host_settings()[4])
+            if holder is not self:
+                sh = _device_f32(shs, "GaussianRasterizer: shs", tuple(shs.shape[1:]), n)
         else:
             colors = _device_f32(colors_precomp, "GaussianRasterizer: colors_precomp", (3,), n)
         opac = _device_f32(opacities, "GaussianRasterizer: opacities", (), n)
@@ -167,22 +274,31 @@ class GaussianRasterizer(torch.nn.Module):
         count = C.c_int64(0)
         with torch.cuda.device(device):
             same = self._key == (n, W, H, device)
-            self._ensure_workspace(lib, n, device, self._capacity if same else 4 * n)      # a first guess: four tiles per Gaussian
+            guess = self._capacity if same else 4 * n      # a first guess: four tiles per Gaussian
+            if holder is not self and self._owned_hint[0] == (n, W, H, device):
+                guess = max(guess, self._owned_hint[1])    # what the last differentiable render of this shape needed
+            _ensure_workspace(holder, lib, n, W, H, device, guess)
             for attempt in (0, 1):
-                d.d_workspace, d.workspace_bytes = self._workspace.data_ptr(), self._workspace.numel()
+                d.d_workspace, d.workspace_bytes = holder._workspace.data_ptr(), holder._workspace.numel()
                 rc = lib.pixie_raster_forward(C.byref(d), C.byref(count), _lib.current_stream_ptr())
                 if rc == 0 or attempt == 1 or count.value <= 0:
                     break
                 # Too small?  Decided in bytes, not instances: the library's sort storage need not grow monotonically with the count.
                 grown = count.value + count.value // 2
                 need = max(lib.pixie_raster_workspace_bytes(n, W, H, count.value), lib.pixie_raster_workspace_bytes(n, W, H, grown))
-                if need <= self._workspace.numel():
+                if need <= holder._workspace.numel():
                     break                                  # the call failed for another reason: report it
-                self._workspace = torch.empty((int(need),), dtype=torch.uint8, device=device)      # grow to 1.5 x and retry once
-                self._capacity = grown
+                holder._workspace = torch.empty((int(need),), dtype=torch.uint8, device=device)      # grow to 1.5 x and retry once
+                holder._capacity = grown
         _lib.check(rc, "pixie_raster_forward", lib=lib)
         self.last_instances = int(count.value)
-        return (out, radii, final_T, n_contrib) if aux else (out, radii)
+        if holder is self:
+            return out, radii, final_T, n_contrib, None
+        self._owned_hint = ((n, W, H, device), holder._capacity)
+        state = dict(desc=d, instances=int(count.value), n=n, W=W, H=H, workspace=holder._workspace, shs=sh, sh_k=0 if sh is None else int(sh.shape[1]),
+                     sh_degree=int(s.sh_degree), campos=[float(x) for x in self._host_settings()[4]],
+                     tensors=[t for t in (means, opac, colors, cov, sc, rot, sh) if t is not None])
+        return out, radii, final_T, n_contrib, state
 
 
 def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=None, unselected=None, rasterizer=None, batch=None):
@@ -193,7 +309,8 @@ def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=
     `unselected`: (pos (M, 3), cov (M, 6)) of Gaussians that do not simulate, appended to every frame (gs_simulation.py:602-606);
     `opacity` and the colours then cover N' = N + M Gaussians.
     `batch`: None renders frame by frame (a call, a colour launch and a stream synchronise per frame); True or a
-    FrameBatchRasterizer hands the sequence to `render_frame_batch`, which gives the same images."""
+    FrameBatchRasterizer hands the sequence to `render_frame_batch`, which gives the same images.
+    Forward only: the frames carry no graph, whatever the inputs require."""
     if batch is not None and batch is not False:
         return render_frame_batch(frames, settings_per_frame, opacity, shs=shs, colors_precomp=colors_precomp, unselected=unselected,
                                   rasterizer=batch if isinstance(batch, FrameBatchRasterizer) else None)
@@ -252,7 +369,7 @@ class FrameBatchRasterizer:
     scan and one stream synchronise for the whole call, then one sort and one render launch per group of views.  The workspace is
     kept between calls.  Its instance capacity starts at four tiles per Gaussian-view, as far as `max_workspace_bytes` allows, and
     grows once when a single view needs more.  After a call `last_instances` holds the per-view instance counts and `last_groups`
-    the number of sort groups."""
+    the number of sort groups.  Forward only: its outputs carry no graph (the differentiable render is `GaussianRasterizer`)."""
 
     def __init__(self, max_workspace_bytes=1 << 30):
         self.max_workspace_bytes = int(max_workspace_bytes)
@@ -433,7 +550,8 @@ def render_frame_batch(frames, settings_per_frame, opacity, shs=None, colors_pre
     workspace's fixed part within half of the rasteriser's `max_workspace_bytes`), with one stream synchronise per call instead of
     one per frame, and without the per-frame concatenation of `unselected`.  Same arguments and argument errors as `render_frames`.
     Returns (F, 3, H, W) float32, bit for bit what `render_frames` gives; `out` fills a given tensor.  `out_rgb8` (True, or a
-    (F, H, W, 3) uint8 tensor) also writes the 8-bit frames `save_frame_png` would; asked for alone, it is what is returned."""
+    (F, H, W, 3) uint8 tensor) also writes the 8-bit frames `save_frame_png` would; asked for alone, it is what is returned.
+    Forward only, like `render_frames`."""
     pos, cov = frames[0], frames[1]
     if cov is None:
         raise ValueError("render_frame_batch: the frames carry no covariance (FrameSchedule.with_cov)")

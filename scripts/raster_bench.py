@@ -6,7 +6,12 @@ count); per-launch times come from running this script under `rocprofv3 --kernel
 `--frames F` times a frame sequence instead: F frames of the ball (it drifts and swells a little from frame to frame) rendered by
 `render_frames`, a call per frame, against one `render_frame_batch` call on the same tensors in the same process, the two
 alternating `--reps` times after `--warmup` rounds of both.  Host clock around each, ending in a device synchronise.  Prints the
-per-view instance counts, the group count, both times and whether the two image sequences are bit-equal."""
+per-view instance counts, the group count, both times and whether the two image sequences are bit-equal.
+
+`--backward` times the differentiable render instead: per size, the forward-only call (under no_grad, as above), then forward +
+backward with means3D, opacities, colors_precomp and cov3D_precomp requiring grad and a fixed dL/dcolour, by HIP events around `--reps`
+iterations after `--warmup`; it prints both next to the bytes of the backward's per-instance buffer (nine floats per instance) and
+whether two backwards gave the same bits.  Per-kernel times come from running it under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import json
 import os
@@ -64,8 +69,43 @@ def time_frames(a, n, st, pos, cov, opacity, colors):
                           workspace_bytes=int(batch._workspace.numel()), bit_equal=bool(torch.equal(out_loop, out_batch)))), flush=True)
 
 
+def time_backward(a, n, r, args, kw):
+    """forward-only against forward + backward on the same inputs"""
+    dev = args[0].device
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    with torch.no_grad():
+        for _ in range(a.warmup):
+            r(*args, **kw)
+        e[0].record()
+        for _ in range(a.reps):
+            r(*args, **kw)
+        e[1].record()
+    means, opac = args[0].clone().requires_grad_(True), args[2].clone().requires_grad_(True)
+    leaves = dict(colors_precomp=kw["colors_precomp"].clone().requires_grad_(True), cov3D_precomp=kw["cov3D_precomp"].clone().requires_grad_(True))
+    means2D = torch.zeros_like(means, requires_grad=True)
+    g = torch.from_numpy(np.random.default_rng(1).uniform(-1, 1, (3, a.size, a.size)).astype(np.float32)).to(dev)
+    params = [means, means2D, opac] + list(leaves.values())
+    first = None
+    for rep in range(a.warmup + a.reps):
+        if rep == a.warmup:
+            e[2].record()
+        for p in params:
+            p.grad = None
+        img, radii = r(means, means2D, opac, **leaves)
+        img.backward(g)
+        if rep == 0:
+            first = [p.grad.clone() for p in params]
+    e[3].record()
+    torch.cuda.synchronize()
+    same = all(torch.equal(x, p.grad) for x, p in zip(first, params))
+    print(json.dumps(dict(n=n, width=a.size, height=a.size, instances=r.last_instances, reps=a.reps, forward_ms=e[0].elapsed_time(e[1]) / a.reps,
+                          forward_backward_ms=e[2].elapsed_time(e[3]) / a.reps, per_instance_buffer_bytes=36 * r.last_instances,
+                          gradients_bit_equal_between_runs=bool(same), device=torch.cuda.get_device_name(0))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--backward", action="store_true", help="time forward + backward of the differentiable render against the forward")
     ap.add_argument("--frames", type=int, default=0, help="time F per-frame calls against one batched call (0: the single-call timing)")
     ap.add_argument("--n", type=int, nargs="+", default=[100_000, 350_000])
     ap.add_argument("--size", type=int, default=800)
@@ -88,6 +128,9 @@ def main():
         r = GaussianRasterizer(st)
         args = (t(pos), None, t(rng.uniform(0.2, 1.0, n).astype(np.float32)))
         kw = dict(colors_precomp=t(rng.uniform(0, 1, (n, 3)).astype(np.float32)), cov3D_precomp=t(cov))
+        if a.backward:
+            time_backward(a, n, r, args, kw)
+            continue
         if a.frames > 0:
             time_frames(a, n, st, args[0], kw["cov3D_precomp"], args[2], kw["colors_precomp"])
             continue

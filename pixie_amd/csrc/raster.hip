@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <climits>
 #include <cstdint>
 #include <vector>
 
@@ -29,21 +28,20 @@
 #include "common.h"
 #include "raster_batch_plan.h"
 #include "raster_math.h"
+#include "raster_tile.h"
 #include "raster_workspace.h"
 
 using namespace pixie;
 namespace rm = pixie::raster;
+using namespace pixie::raster_tile;
 using namespace pixie::raster_ws;
 
 namespace {
 
-constexpr int kBlock = 256;               // = kTile * kTile: one lane per pixel of a tile
-
 __global__ void __launch_bounds__(kBlock)
-raster_preprocess_kernel(int n, rm::Camera cam, const float* __restrict__ means, const float* __restrict__ cov3d,
-                         const float* __restrict__ scales, const float* __restrict__ rotations, float scale_modifier,
-                         const float* __restrict__ opacity, float* __restrict__ depth, float2* __restrict__ centre,
-                         float4* __restrict__ conic_opacity, int32_t* __restrict__ radii, uint64_t* __restrict__ tiles_touched) {
+raster_preprocess_kernel(int n, rm::Camera cam, const float* __restrict__ means, const float* __restrict__ cov3d, const float* __restrict__ scales,
+                         const float* __restrict__ rotations, float scale_modifier, const float* __restrict__ opacity, float* __restrict__ depth,
+                         float2* __restrict__ centre, float4* __restrict__ conic_opacity, int32_t* __restrict__ radii, uint64_t* __restrict__ tiles_touched) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i > n) return;
     if (i == n) { tiles_touched[n] = 0; return; }    // the scan runs over n + 1 counts
@@ -58,39 +56,18 @@ raster_preprocess_kernel(int n, rm::Camera cam, const float* __restrict__ means,
         rm::cov3d_from_scale_rot(s, scale_modifier, q, c6);
     }
     rm::Splat2D o;
-    if (!rm::project(p, c6, cam, o)) {
-        radii[i] = 0;
-        tiles_touched[i] = 0;
-        return;
-    }
-    depth[i] = o.depth;
-    centre[i] = make_float2(o.px, o.py);
-    conic_opacity[i] = make_float4(o.ca, o.cb, o.cc, opacity[i]);
-    radii[i] = o.radius;
-    tiles_touched[i] = (uint64_t)((o.x1 - o.x0) * (o.y1 - o.y0));
+    if (!rm::project(p, c6, cam, o)) { store_projection((size_t)i, i, nullptr, opacity, depth, centre, conic_opacity, radii, tiles_touched); return; }
+    store_projection((size_t)i, i, &o, opacity, depth, centre, conic_opacity, radii, tiles_touched);
 }
 
 __global__ void __launch_bounds__(kBlock)
-raster_duplicate_kernel(int n, int tiles_x, int tiles_y, const float2* __restrict__ centre, const float* __restrict__ depth,
-                        const int32_t* __restrict__ radii, const uint64_t* __restrict__ offsets, uint64_t* __restrict__ keys,
-                        uint32_t* __restrict__ values) {
+raster_duplicate_kernel(int n, int tiles_x, int tiles_y, const float2* __restrict__ centre, const float* __restrict__ depth, const int32_t* __restrict__ radii,
+                        const uint64_t* __restrict__ offsets, uint64_t* __restrict__ keys, uint32_t* __restrict__ values) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const int r = radii[i];
     if (r <= 0) return;
-    const float2 c = centre[i];
-    int x0, y0, x1, y1;
-    rm::tile_rect(c.x, c.y, r, tiles_x, tiles_y, x0, y0, x1, y1);
-    uint64_t off = offsets[i];
-    const uint64_t end = offsets[i + 1];             // never written past: the rectangle is the one preprocess counted
-    const uint64_t dbits = (uint64_t)__float_as_uint(depth[i]);
-    for (int y = y0; y < y1; ++y)
-        for (int x = x0; x < x1; ++x) {
-            if (off >= end) return;
-            keys[off] = ((uint64_t)(uint32_t)(y * tiles_x + x) << 32) | dbits;
-            values[off] = (uint32_t)i;
-            ++off;
-        }
+    emit_instances(centre[i], r, (uint64_t)__float_as_uint(depth[i]), tiles_x, tiles_y, 0u, (uint32_t)i, offsets[i], offsets[i + 1], keys, values);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -111,45 +88,21 @@ raster_ranges_kernel(int64_t count, const uint64_t* __restrict__ keys, uint2* __
 }
 
 __global__ void __launch_bounds__(kBlock)
-raster_render_kernel(int W, int H, int tiles_x, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-                     const float2* __restrict__ centre, const float4* __restrict__ conic_opacity, const float* __restrict__ colors,
-                     float bg0, float bg1, float bg2, float* __restrict__ out_color, float* __restrict__ final_T,
-                     int32_t* __restrict__ n_contrib) {
+raster_render_kernel(int W, int H, int tiles_x, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float2* __restrict__ centre,
+                     const float4* __restrict__ conic_opacity, const float* __restrict__ colors, float bg0, float bg1, float bg2,
+                     float* __restrict__ out_color, float* __restrict__ final_T, int32_t* __restrict__ n_contrib) {
     __shared__ float2 s_xy[kBlock];
     __shared__ float4 s_co[kBlock];
     __shared__ float3 s_rgb[kBlock];
-    const int tid = threadIdx.x;                     // wave w owns rows 4w .. 4w+3 of the tile
-    const int pix_x = blockIdx.x * rm::kTile + (tid & (rm::kTile - 1));
-    const int pix_y = blockIdx.y * rm::kTile + (tid >> 4);
-    const bool inside = pix_x < W && pix_y < H;
-    const float fx = (float)pix_x, fy = (float)pix_y;
-    const uint2 range = ranges[blockIdx.y * tiles_x + blockIdx.x];
-    int todo = (int)(range.y - range.x);
-    rm::PixelAcc acc = rm::pixel_start(!inside);
-
-    for (uint32_t base = range.x; base < range.y; base += kBlock, todo -= kBlock) {
-        if (__syncthreads_count(acc.done) == kBlock) break;      // also the barrier that frees the staging buffers
-        if (base + tid < range.y) {
-            const uint32_t g = point_list[base + tid];
-            s_xy[tid] = centre[g];
-            s_co[tid] = conic_opacity[g];
-            s_rgb[tid] = make_float3(colors[(size_t)g * 3], colors[(size_t)g * 3 + 1], colors[(size_t)g * 3 + 2]);
-        }
-        __syncthreads();
-        const int cnt = todo < kBlock ? todo : kBlock;
-        for (int j = 0; !acc.done && j < cnt; ++j) {
-            const float2 xy = s_xy[j];
-            const float4 co = s_co[j];
-            const float3 rgb = s_rgb[j];
-            rm::blend(acc, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, fx, fy);
-        }
-    }
-    if (inside) {
-        const size_t pix = (size_t)pix_y * W + pix_x;
+    const TilePixel px = tile_pixel(W, H);
+    const rm::PixelAcc acc = forward_walk(tile_range(ranges, tiles_x, 0), px, point_list, centre, conic_opacity, colors, 0u, s_xy, s_co, s_rgb);
+    if (px.inside) {
+        const size_t pix = (size_t)px.y * W + px.x;
         const size_t plane = (size_t)W * H;
-        out_color[pix] = acc.r + acc.T * bg0;
-        out_color[plane + pix] = acc.g + acc.T * bg1;
-        out_color[2 * plane + pix] = acc.b + acc.T * bg2;
+        const float3 c = composite(acc, bg0, bg1, bg2);
+        out_color[pix] = c.x;
+        out_color[plane + pix] = c.y;
+        out_color[2 * plane + pix] = c.z;
         if (final_T) final_T[pix] = acc.T;
         if (n_contrib) n_contrib[pix] = (int32_t)acc.last;
     }
@@ -160,26 +113,8 @@ sh_to_rgb_kernel(const float* __restrict__ shs, int64_t n, int k_coeffs, int deg
                  float cz, const float* __restrict__ rot, int64_t n_rot, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    float dx = pos[i * 3] - cx, dy = pos[i * 3 + 1] - cy, dz = pos[i * 3 + 2] - cz;
-    if (i < n_rot) {
-        const float* R = rot + i * 9;
-        const float rx = R[0] * dx + R[1] * dy + R[2] * dz;
-        const float ry = R[3] * dx + R[4] * dy + R[5] * dz;
-        const float rz = R[6] * dx + R[7] * dy + R[8] * dz;
-        dx = rx; dy = ry; dz = rz;
-    }
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    float rgb[3];
-    rm::sh_to_rgb(shs + i * k_coeffs * 3, degree, dx / len, dy / len, dz / len, rgb);
-    for (int d = 0; d < 3; ++d) out[i * 3 + d] = rgb[d];
-}
-
-int check_shape(const char* who, int n, int width, int height) {
-    PX_REQUIRE(n >= 0, "%s: n %d < 0", who, n);
-    PX_REQUIRE(n < INT_MAX, "%s: n %d exceeds one scan (n + 1 counts)", who, n);
-    PX_REQUIRE(width > 0 && height > 0, "%s: image %d x %d must be positive", who, width, height);
-    PX_REQUIRE(width <= 65536 && height <= 65536, "%s: image %d x %d exceeds 65536 per side", who, width, height);
-    return 0;
+    const float campos[3] = {cx, cy, cz};
+    sh_colour(shs + i * k_coeffs * 3, degree, pos + i * 3, campos, i < n_rot ? rot + i * 9 : nullptr, out + i * 3);
 }
 
 // ------------------------------------------------------------------------------------------------ a batch of views
@@ -204,9 +139,8 @@ struct BatchGeom {
 // the colour of every Gaussian that survives the projection, as sh_to_rgb_kernel does without a rotation.
 __global__ void __launch_bounds__(kBlock)
 raster_batch_preprocess_kernel(BatchGeom geo, int views, const ViewCam* __restrict__ cams, const float* __restrict__ opacity,
-                               const float* __restrict__ shs, int k_coeffs, int sh_degree, float* __restrict__ depth,
-                               float2* __restrict__ centre, float4* __restrict__ conic_opacity, int32_t* __restrict__ radii,
-                               float* __restrict__ rgb, uint64_t* __restrict__ tiles_touched) {
+                               const float* __restrict__ shs, int k_coeffs, int sh_degree, float* __restrict__ depth, float2* __restrict__ centre,
+                               float4* __restrict__ conic_opacity, int32_t* __restrict__ radii, float* __restrict__ rgb, uint64_t* __restrict__ tiles_touched) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const int v = blockIdx.y;
     const int n = geo.n;
@@ -223,23 +157,10 @@ raster_batch_preprocess_kernel(BatchGeom geo, int views, const ViewCam* __restri
     for (int d = 0; d < 6; ++d) c6[d] = cp[d];
     const ViewCam& vc = cams[v];
     rm::Splat2D o;
-    if (!rm::project(p, c6, vc.cam, o)) {
-        radii[G] = 0;
-        tiles_touched[G] = 0;
-        return;
-    }
-    depth[G] = o.depth;
-    centre[G] = make_float2(o.px, o.py);
-    conic_opacity[G] = make_float4(o.ca, o.cb, o.cc, opacity[i]);
-    radii[G] = o.radius;
-    tiles_touched[G] = (uint64_t)((o.x1 - o.x0) * (o.y1 - o.y0));
-    if (shs) {
-        const float dx = p[0] - vc.campos[0], dy = p[1] - vc.campos[1], dz = p[2] - vc.campos[2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        float c[3];
-        rm::sh_to_rgb(shs + (size_t)i * k_coeffs * 3, sh_degree, dx / len, dy / len, dz / len, c);
-        for (int d = 0; d < 3; ++d) rgb[G * 3 + d] = c[d];
-    }
+    if (!rm::project(p, c6, vc.cam, o)) { store_projection(G, i, nullptr, opacity, depth, centre, conic_opacity, radii, tiles_touched); return; }
+    store_projection(G, i, &o, opacity, depth, centre, conic_opacity, radii, tiles_touched);
+    if (shs)
+        sh_colour(shs + (size_t)i * k_coeffs * 3, sh_degree, p, vc.campos, nullptr, rgb + G * 3);
 }
 
 // bounds[v] = offsets[v * n], v = 0 .. views: the instance offsets at the view boundaries, the only thing the host reads back
@@ -260,81 +181,43 @@ raster_batch_duplicate_kernel(int n, int v0, int tiles_x, int tiles_y, uint64_t 
     const size_t G = (size_t)(v0 + vg) * n + i;
     const int r = radii[G];
     if (r <= 0) return;
-    const float2 c = centre[G];
-    int x0, y0, x1, y1;
-    rm::tile_rect(c.x, c.y, r, tiles_x, tiles_y, x0, y0, x1, y1);
-    uint64_t off = offsets[G] - group_base;
-    uint64_t end = offsets[G + 1] - group_base;      // never written past: the rectangle is the one preprocess counted,
-    if (end > group_count) end = group_count;        // and never past what the host sized the group's buffers for
-    const uint64_t dbits = (uint64_t)__float_as_uint(depth[G]);
-    const uint32_t tile0 = (uint32_t)vg * (uint32_t)(tiles_x * tiles_y);
-    for (int y = y0; y < y1; ++y)
-        for (int x = x0; x < x1; ++x) {
-            if (off >= end) return;
-            keys[off] = ((uint64_t)(tile0 + (uint32_t)(y * tiles_x + x)) << 32) | dbits;
-            values[off] = (uint32_t)((size_t)vg * n + i);
-            ++off;
-        }
+    uint64_t end = offsets[G + 1] - group_base;
+    if (end > group_count) end = group_count;        // never past what the host sized the group's buffers for
+    emit_instances(centre[G], r, (uint64_t)__float_as_uint(depth[G]), tiles_x, tiles_y, (uint32_t)vg * (uint32_t)(tiles_x * tiles_y),
+                   (uint32_t)((size_t)vg * n + i), offsets[G] - group_base, end, keys, values);
 }
 
-// raster_render_kernel on a (tiles_x, tiles_y, views in group) grid: the same staging, the same blend loop and the same
-// compositing expression per view; the epilogue also writes the 8-bit frame where one is asked for.
+// raster_render_kernel on a (tiles_x, tiles_y, views in group) grid: the same walk and the same compositing per view; the epilogue
+// also writes the 8-bit frame where one is asked for.
 __global__ void __launch_bounds__(kBlock)
-raster_batch_render_kernel(int W, int H, int tiles_x, int tiles_y, int n, int v0, const uint2* __restrict__ ranges,
-                           const uint32_t* __restrict__ point_list, const float2* __restrict__ centre,
-                           const float4* __restrict__ conic_opacity, const float* __restrict__ colors, int64_t colors_stride, float bg0,
-                           float bg1, float bg2, float* __restrict__ out_color, uint8_t* __restrict__ out_rgb8,
+raster_batch_render_kernel(int W, int H, int tiles_x, int tiles_y, int n, int v0, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+                           const float2* __restrict__ centre, const float4* __restrict__ conic_opacity, const float* __restrict__ colors,
+                           int64_t colors_stride, float bg0, float bg1, float bg2, float* __restrict__ out_color, uint8_t* __restrict__ out_rgb8,
                            float* __restrict__ final_T, int32_t* __restrict__ n_contrib) {
     __shared__ float2 s_xy[kBlock];
     __shared__ float4 s_co[kBlock];
     __shared__ float3 s_rgb[kBlock];
-    const int tid = threadIdx.x;
     const int vg = blockIdx.z;
     const size_t view = (size_t)(v0 + vg);
-    const int pix_x = blockIdx.x * rm::kTile + (tid & (rm::kTile - 1));
-    const int pix_y = blockIdx.y * rm::kTile + (tid >> 4);
-    const bool inside = pix_x < W && pix_y < H;
-    const float fx = (float)pix_x, fy = (float)pix_y;
-    const uint2 range = ranges[(size_t)vg * (tiles_x * tiles_y) + blockIdx.y * tiles_x + blockIdx.x];
-    int todo = (int)(range.y - range.x);
-    rm::PixelAcc acc = rm::pixel_start(!inside);
     const size_t gbase = (size_t)v0 * n;                        // g -> G
-    const float* vcolors = colors + view * colors_stride;       // this view's [n][3]
-    const uint32_t g0 = (uint32_t)((size_t)vg * n);             // g -> i
-
-    for (uint32_t base = range.x; base < range.y; base += kBlock, todo -= kBlock) {
-        if (__syncthreads_count(acc.done) == kBlock) break;
-        if (base + tid < range.y) {
-            const uint32_t g = point_list[base + tid];
-            s_xy[tid] = centre[gbase + g];
-            s_co[tid] = conic_opacity[gbase + g];
-            const size_t ci = (size_t)(g - g0) * 3;
-            s_rgb[tid] = make_float3(vcolors[ci], vcolors[ci + 1], vcolors[ci + 2]);
-        }
-        __syncthreads();
-        const int cnt = todo < kBlock ? todo : kBlock;
-        for (int j = 0; !acc.done && j < cnt; ++j) {
-            const float2 xy = s_xy[j];
-            const float4 co = s_co[j];
-            const float3 rgb = s_rgb[j];
-            rm::blend(acc, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, fx, fy);
-        }
-    }
-    if (inside) {
-        const size_t pix = (size_t)pix_y * W + pix_x;
+    const TilePixel px = tile_pixel(W, H);
+    const rm::PixelAcc acc = forward_walk(tile_range(ranges, tiles_x, (size_t)vg * (tiles_x * tiles_y)), px, point_list, centre + gbase,
+                                          conic_opacity + gbase, colors + view * colors_stride, (uint32_t)((size_t)vg * n), s_xy, s_co, s_rgb);
+    if (px.inside) {
+        const size_t pix = (size_t)px.y * W + px.x;
         const size_t plane = (size_t)W * H;
-        const float r = acc.r + acc.T * bg0, g = acc.g + acc.T * bg1, b = acc.b + acc.T * bg2;
+        const float3 c = composite(acc, bg0, bg1, bg2);
         if (out_color) {
             float* oc = out_color + view * 3 * plane;
-            oc[pix] = r;
-            oc[plane + pix] = g;
-            oc[2 * plane + pix] = b;
+            oc[pix] = c.x;
+            oc[plane + pix] = c.y;
+            oc[2 * plane + pix] = c.z;
         }
         if (out_rgb8) {
             uint8_t* o8 = out_rgb8 + (view * plane + pix) * 3;
-            o8[0] = (uint8_t)rintf(fminf(fmaxf(255.0f * r, 0.0f), 255.0f));
-            o8[1] = (uint8_t)rintf(fminf(fmaxf(255.0f * g, 0.0f), 255.0f));
-            o8[2] = (uint8_t)rintf(fminf(fmaxf(255.0f * b, 0.0f), 255.0f));
+            o8[0] = (uint8_t)rintf(fminf(fmaxf(255.0f * c.x, 0.0f), 255.0f));
+            o8[1] = (uint8_t)rintf(fminf(fmaxf(255.0f * c.y, 0.0f), 255.0f));
+            o8[2] = (uint8_t)rintf(fminf(fmaxf(255.0f * c.z, 0.0f), 255.0f));
         }
         if (final_T) final_T[view * plane + pix] = acc.T;
         if (n_contrib) n_contrib[view * plane + pix] = (int32_t)acc.last;
@@ -342,24 +225,12 @@ raster_batch_render_kernel(int W, int H, int tiles_x, int tiles_y, int n, int v0
 }
 
 // Workspace of a batch: what the projection and the scan of views * n Gaussian-views need, then one group's sort storage.
-struct BatchLayout {
-    size_t cams, depth, centre, conic_opacity, radii, rgb, tiles_touched, offsets, bounds, ranges, scan_temp, scan_temp_bytes, fixed_bytes;
-    size_t keys_in, keys_out, vals_in, vals_out, sort_temp, total_bytes;
+struct BatchLayout : SortLayout {
+    size_t cams, depth, centre, conic_opacity, radii, rgb, tiles_touched, offsets, bounds, ranges, scan_temp, scan_temp_bytes, fixed_bytes, total_bytes;
     int max_group_views;
 };
 
 constexpr int kSortProbes = 16;
-
-// the sort's temporary storage for `m` instances of `group_views` views
-int sort_temp_bytes(size_t m, int64_t group_tiles, size_t& bytes) {
-    bytes = 0;
-    if (m == 0) return 0;
-    int bits = 0;
-    while ((1LL << bits) < group_tiles) ++bits;
-    PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                                    (uint32_t*)nullptr, m, 0, 32 + bits));
-    return 0;
-}
 
 int make_batch_layout(int n, int views, int tiles, int64_t instances, BatchLayout& L) {
     const size_t total = (size_t)views * (size_t)n;
@@ -381,10 +252,6 @@ int make_batch_layout(int n, int views, int tiles, int64_t instances, BatchLayou
     L.scan_temp = take(cur, L.scan_temp_bytes);
     L.fixed_bytes = cur;
     const size_t m = (size_t)instances;
-    L.keys_in = take(cur, sizeof(uint64_t) * m);
-    L.keys_out = take(cur, sizeof(uint64_t) * m);
-    L.vals_in = take(cur, sizeof(uint32_t) * m);
-    L.vals_out = take(cur, sizeof(uint32_t) * m);
     // A group may hold any count up to m, and the library's storage need not grow monotonically with the count: take the largest
     // of a ladder of counts.  The call still checks each group's own need against what is left behind L.sort_temp.
     size_t temp = 0;
@@ -393,7 +260,7 @@ int make_batch_layout(int n, int views, int tiles, int64_t instances, BatchLayou
         if (sort_temp_bytes((m * k + kSortProbes - 1) / kSortProbes, (int64_t)L.max_group_views * tiles, b)) return 1;
         if (b > temp) temp = b;
     }
-    L.sort_temp = take(cur, temp);
+    take_sort(cur, m, temp, L);
     L.total_bytes = cur;
     return 0;
 }
@@ -406,16 +273,25 @@ int check_batch_shape(const char* who, int n, int views, int width, int height, 
     return 0;
 }
 
+// One sort group: sorts the `count` (key, value) pairs that a duplicate kernel left in S.keys_in / S.vals_in over `tiles` tiles (all
+// the views of the group) and marks where each tile's run starts and ends in `ranges`, which the caller has zeroed.
+int sort_group(char* ws, const SortLayout& S, uint64_t count, int64_t tiles, uint2* ranges, hipStream_t st) {
+    size_t tb = 0;
+    if (sort_temp_bytes((size_t)count, tiles, tb)) return 1;
+    uint64_t* keys_out = (uint64_t*)(ws + S.keys_out);
+    PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + S.sort_temp, tb, (const uint64_t*)(ws + S.keys_in), keys_out, (const uint32_t*)(ws + S.vals_in),
+                                                    (uint32_t*)(ws + S.vals_out), (size_t)count, 0, key_bits(tiles), st));
+    hipLaunchKernelGGL(raster_ranges_kernel, dim3(cdiv((long)count, kBlock)), dim3(kBlock), 0, st, (int64_t)count, keys_out, ranges);
+    PX_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t pixie_raster_workspace_bytes(int n, int width, int height, int64_t max_instances) {
-    if (check_shape("pixie_raster_workspace_bytes", n, width, height)) return -1;
-    if (max_instances < 0 || max_instances > (int64_t)UINT32_MAX) {
-        set_error("pixie_raster_workspace_bytes: max_instances %lld outside [0, 2^32)", (long long)max_instances);
-        return -1;
-    }
+    if (check_batch_shape("pixie_raster_workspace_bytes", n, 1, width, height, max_instances)) return -1;      // one view
     const int tiles = cdiv(width, rm::kTile) * cdiv(height, rm::kTile);
     Layout L;
     if (make_layout(n, tiles, max_instances, L)) return -1;
@@ -425,17 +301,8 @@ int64_t pixie_raster_workspace_bytes(int n, int width, int height, int64_t max_i
 int pixie_raster_forward(const pixie_raster_desc* d, int64_t* instances_out, void* stream) {
     PX_REQUIRE(d, "pixie_raster_forward: null descriptor");
     if (instances_out) *instances_out = 0;
-    if (check_shape("pixie_raster_forward", d->n, d->width, d->height)) return 1;
-    PX_REQUIRE(d->tanfovx > 0.0f && d->tanfovy > 0.0f, "pixie_raster_forward: tanfovx %g, tanfovy %g must be positive", d->tanfovx, d->tanfovy);
-    PX_REQUIRE(d->d_out_color, "pixie_raster_forward: null pointer (d_out_color is required)");
+    if (check_forward_desc("pixie_raster_forward", "", *d)) return 1;
     const int n = d->n;
-    if (n > 0) {
-        PX_REQUIRE(d->d_means && d->d_colors && d->d_opacity && d->d_radii,
-                   "pixie_raster_forward: null pointer (d_means, d_colors, d_opacity and d_radii are required)");
-        PX_REQUIRE((d->d_cov3d != nullptr) != (d->d_scales != nullptr || d->d_rotations != nullptr),
-                   "pixie_raster_forward: give either d_cov3d or the pair d_scales, d_rotations");
-        PX_REQUIRE(d->d_cov3d || (d->d_scales && d->d_rotations), "pixie_raster_forward: d_scales and d_rotations go together");
-    }
     const rm::Camera cam = rm::make_camera(d->viewmatrix, d->projmatrix, d->tanfovx, d->tanfovy, d->width, d->height);
     const int tiles = cam.tiles_x * cam.tiles_y;
     Layout L;
@@ -466,28 +333,19 @@ int pixie_raster_forward(const pixie_raster_desc* d, int64_t* instances_out, voi
     if (instances_out) *instances_out = (int64_t)count;
     PX_REQUIRE(count <= (uint64_t)UINT32_MAX, "pixie_raster_forward: %llu instances exceed 2^32", (unsigned long long)count);
     if (make_layout(n, tiles, (int64_t)count, L)) return 1;
-    PX_REQUIRE((int64_t)L.total_bytes <= d->workspace_bytes,
-               "pixie_raster_forward: workspace too small: %llu instances need %lld bytes, the workspace has %lld",
+    PX_REQUIRE((int64_t)L.total_bytes <= d->workspace_bytes, "pixie_raster_forward: workspace too small: %llu instances need %lld bytes, the workspace has %lld",
                (unsigned long long)count, (long long)L.total_bytes, (long long)d->workspace_bytes);
 
     PX_CHECK_HIP(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)tiles, st));
     uint32_t* sorted_vals = (uint32_t*)(ws + L.vals_out);
     if (count > 0) {
-        uint64_t* keys_in = (uint64_t*)(ws + L.keys_in);
-        uint64_t* keys_out = (uint64_t*)(ws + L.keys_out);
-        uint32_t* vals_in = (uint32_t*)(ws + L.vals_in);
         hipLaunchKernelGGL(raster_duplicate_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st, n, cam.tiles_x, cam.tiles_y, centre, depth,
-                           d->d_radii, offsets, keys_in, vals_in);
+                           d->d_radii, offsets, (uint64_t*)(ws + L.keys_in), (uint32_t*)(ws + L.vals_in));
         PX_CHECK_HIP(hipGetLastError());
-        size_t tb = L.sort_temp_bytes;
-        PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.sort_temp, tb, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
-                                                        sorted_vals, (size_t)count, 0, sort_end_bit(tiles), st));
-        hipLaunchKernelGGL(raster_ranges_kernel, dim3(cdiv((long)count, kBlock)), dim3(kBlock), 0, st, (int64_t)count, keys_out, ranges);
-        PX_CHECK_HIP(hipGetLastError());
+        if (sort_group(ws, L, count, tiles, ranges, st)) return 1;
     }
-    hipLaunchKernelGGL(raster_render_kernel, dim3(cam.tiles_x, cam.tiles_y), dim3(kBlock), 0, st, d->width, d->height, cam.tiles_x, ranges,
-                       sorted_vals, centre, conic_opacity, d->d_colors, d->bg[0], d->bg[1], d->bg[2], d->d_out_color, d->d_final_T,
-                       d->d_n_contrib);
+    hipLaunchKernelGGL(raster_render_kernel, dim3(cam.tiles_x, cam.tiles_y), dim3(kBlock), 0, st, d->width, d->height, cam.tiles_x, ranges, sorted_vals,
+                       centre, conic_opacity, d->d_colors, d->bg[0], d->bg[1], d->bg[2], d->d_out_color, d->d_final_T, d->d_n_contrib);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -576,11 +434,7 @@ int pixie_raster_forward_batch(const pixie_raster_batch_desc* d, int64_t* instan
         }
         // host_cams and bounds outlive both copies: the synchronise below comes before either goes out of scope
         PX_CHECK_HIP(hipMemcpyAsync(ws + L.cams, host_cams.data(), sizeof(ViewCam) * (size_t)views, hipMemcpyHostToDevice, st));
-        BatchGeom geo;
-        geo.means = d->d_means; geo.cov3d = d->d_cov3d;
-        geo.means_stride = d->means_view_stride; geo.cov3d_stride = d->cov3d_view_stride;
-        geo.static_means = d->d_static_means; geo.static_cov3d = d->d_static_cov3d;
-        geo.n = n; geo.n_dyn = d->n_dyn;
+        const BatchGeom geo = {d->d_means, d->d_cov3d, d->means_view_stride, d->cov3d_view_stride, d->d_static_means, d->d_static_cov3d, n, d->n_dyn};
         hipLaunchKernelGGL(raster_batch_preprocess_kernel, dim3(cdiv((long)n + 1, kBlock), views), dim3(kBlock), 0, st, geo, views, cams,
                            d->d_opacity, d->d_shs, d->k_coeffs, d->sh_degree, depth, centre, conic_opacity, radii, rgb, tiles_touched);
         PX_CHECK_HIP(hipGetLastError());
@@ -604,18 +458,15 @@ int pixie_raster_forward_batch(const pixie_raster_batch_desc* d, int64_t* instan
     }
     // every group's sort must find its temporary storage behind L.sort_temp before anything is rendered
     const size_t temp_room = (size_t)d->workspace_bytes - L.sort_temp;
-    std::vector<size_t> temp_need((size_t)groups, 0);
     for (int64_t k = 0; k < groups; ++k) {
         const uint64_t count = bounds[begin[k + 1]] - bounds[begin[k]];
-        if (sort_temp_bytes((size_t)count, (int64_t)(begin[k + 1] - begin[k]) * tiles, temp_need[k])) return 1;
-        PX_REQUIRE(temp_need[k] <= temp_room, "%s: workspace too small: sorting the %llu instances of views %d..%d needs %llu bytes of temporary storage, %llu are left",
-                   who, (unsigned long long)count, begin[k], begin[k + 1] - 1, (unsigned long long)temp_need[k], (unsigned long long)temp_room);
+        size_t need = 0;
+        if (sort_temp_bytes((size_t)count, (int64_t)(begin[k + 1] - begin[k]) * tiles, need)) return 1;
+        PX_REQUIRE(need <= temp_room, "%s: workspace too small: sorting the %llu instances of views %d..%d needs %llu bytes of temporary storage, %llu are left",
+                   who, (unsigned long long)count, begin[k], begin[k + 1] - 1, (unsigned long long)need, (unsigned long long)temp_room);
     }
     if (groups_out) *groups_out = (int32_t)groups;
 
-    uint64_t* keys_in = (uint64_t*)(ws + L.keys_in);
-    uint64_t* keys_out = (uint64_t*)(ws + L.keys_out);
-    uint32_t* vals_in = (uint32_t*)(ws + L.vals_in);
     uint32_t* sorted_vals = (uint32_t*)(ws + L.vals_out);
     const float* colors = d->d_shs ? rgb : d->d_colors;
     const int64_t colors_stride = d->d_shs ? (int64_t)n * 3 : d->colors_view_stride;
@@ -626,15 +477,9 @@ int pixie_raster_forward_batch(const pixie_raster_batch_desc* d, int64_t* instan
         PX_CHECK_HIP(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)group_tiles, st));
         if (count > 0) {
             hipLaunchKernelGGL(raster_batch_duplicate_kernel, dim3(cdiv(n, kBlock), gv), dim3(kBlock), 0, st, n, v0, tiles_x, tiles_y, bounds[v0],
-                               count, centre, depth, radii, offsets, keys_in, vals_in);
+                               count, centre, depth, radii, offsets, (uint64_t*)(ws + L.keys_in), (uint32_t*)(ws + L.vals_in));
             PX_CHECK_HIP(hipGetLastError());
-            size_t tb = temp_need[k];
-            int bits = 0;
-            while ((1LL << bits) < group_tiles) ++bits;
-            PX_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.sort_temp, tb, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
-                                                            sorted_vals, (size_t)count, 0, 32 + bits, st));
-            hipLaunchKernelGGL(raster_ranges_kernel, dim3(cdiv((long)count, kBlock)), dim3(kBlock), 0, st, (int64_t)count, keys_out, ranges);
-            PX_CHECK_HIP(hipGetLastError());
+            if (sort_group(ws, L, count, group_tiles, ranges, st)) return 1;
         }
         hipLaunchKernelGGL(raster_batch_render_kernel, dim3(tiles_x, tiles_y, gv), dim3(kBlock), 0, st, d->width, d->height, tiles_x, tiles_y, n,
                            v0, ranges, sorted_vals, centre, conic_opacity, colors, colors_stride, d->bg[0], d->bg[1], d->bg[2], d->d_out_color,

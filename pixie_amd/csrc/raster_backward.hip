@@ -11,27 +11,27 @@
 // largest n_contrib, and each lane ignores instances past its own.  Per staged Gaussian the nine partials are reduced over the tile in
 // a fixed order: a butterfly over the wave (skipped when no lane of the wave contributes), then the four waves' partials through LDS,
 // summed in wave order, and one lane writes the tile's nine floats to the per-instance buffer at slot offsets[g] + k, k being the
-// tile's position in g's rectangle in the order raster_duplicate_kernel enumerates it.  No floating-point atomics anywhere: gradients
+// tile's position in g's rectangle (raster_tile.h: instance_slot beside the duplicate kernels' emit_instances).  No floating-point atomics: gradients
 // are bit-identical from run to run.  The gather kernel sums each Gaussian's contiguous segment sequentially and applies the
 // per-Gaussian chain of raster_grad_math.h (projection, covariance, spherical harmonics).
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
 #include "raster_grad_math.h"
 #include "raster_math.h"
+#include "raster_tile.h"
 #include "raster_workspace.h"
 
 using namespace pixie;
+using namespace pixie::raster_tile;
 using namespace pixie::raster_ws;
 namespace rm = pixie::raster;
 
 namespace {
 
-constexpr int kBlock = 256;               // = kTile * kTile: one lane per pixel of a tile
 constexpr int kWaves = kBlock / 64;
 constexpr int kG = rm::kSampleGrads;
 
@@ -48,19 +48,16 @@ raster_render_backward_kernel(int W, int H, int tiles_x, int tiles_y, int n, uin
     __shared__ int s_max;
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
-    const int pix_x = blockIdx.x * rm::kTile + (tid & (rm::kTile - 1));
-    const int pix_y = blockIdx.y * rm::kTile + (tid >> 4);
-    const bool inside = pix_x < W && pix_y < H;
-    const float fx = (float)pix_x, fy = (float)pix_y;
-    const uint2 range = ranges[blockIdx.y * tiles_x + blockIdx.x];
+    const TilePixel px = tile_pixel(W, H);
+    const uint2 range = tile_range(ranges, tiles_x, 0);
 
     rm::PixelGradWalk walk;
     walk.T = 1.0f; walk.r = walk.g = walk.b = 0.0f;
     walk.out_r = walk.out_g = walk.out_b = 0.0f;
     walk.gr = walk.gg = walk.gb = 0.0f;
     int last = 0;                                    // instances [0, last) of the tile's run are this pixel's to visit
-    if (inside) {
-        const size_t pix = (size_t)pix_y * W + pix_x;
+    if (px.inside) {
+        const size_t pix = (size_t)px.y * W + px.x;
         const size_t plane = (size_t)W * H;
         last = n_contrib[pix];
         walk.out_r = out_color[pix]; walk.out_g = out_color[plane + pix]; walk.out_b = out_color[2 * plane + pix];
@@ -80,13 +77,8 @@ raster_render_backward_kernel(int W, int H, int tiles_x, int tiles_y, int n, uin
             uint32_t g = point_list[range.x + (uint32_t)start + (uint32_t)tid];
             const bool sane = g < (uint32_t)n;       // a workspace that is not the forward's must not send a load or store astray
             if (!sane) g = 0u;
-            const float2 c = centre[g];
-            s_xy[tid] = c;
-            s_co[tid] = conic_opacity[g];
-            s_rgb[tid] = make_float3(colors[(size_t)g * 3], colors[(size_t)g * 3 + 1], colors[(size_t)g * 3 + 2]);
-            int x0, y0, x1, y1;
-            rm::tile_rect(c.x, c.y, radii[g], tiles_x, tiles_y, x0, y0, x1, y1);
-            const uint64_t slot = offsets[g] + (uint64_t)(((int)blockIdx.y - y0) * (x1 - x0) + ((int)blockIdx.x - x0));
+            const float2 c = stage_instance(tid, g, 0u, centre, conic_opacity, colors, s_xy, s_co, s_rgb);
+            const uint64_t slot = instance_slot(c, radii[g], tiles_x, tiles_y, (int)blockIdx.x, (int)blockIdx.y, offsets[g]);
             s_slot[tid] = sane ? slot : instances;
         }
         __syncthreads();
@@ -98,7 +90,7 @@ raster_render_backward_kernel(int W, int H, int tiles_x, int tiles_y, int n, uin
                 const float2 xy = s_xy[j];
                 const float4 co = s_co[j];
                 const float3 rgb = s_rgb[j];
-                hit = rm::sample_backward(walk, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, fx, fy, d);
+                hit = rm::sample_backward(walk, xy.x, xy.y, co.x, co.y, co.z, co.w, rgb.x, rgb.y, rgb.z, px.fx, px.fy, d);
             }
             if (__ballot(hit) != 0ull) {             // wave-uniform
                 for (int q = 0; q < kG; ++q) {
@@ -230,21 +222,14 @@ int pixie_raster_backward(const pixie_raster_backward_desc* d, void* stream) {
     PX_REQUIRE(d, "%s: null descriptor", who);
     const pixie_raster_desc& f = d->forward;
     const int n = f.n;
-    PX_REQUIRE(n >= 0 && n < INT_MAX, "%s: forward.n %d outside [0, 2^31 - 1)", who, n);
-    PX_REQUIRE(f.width > 0 && f.height > 0 && f.width <= 65536 && f.height <= 65536, "%s: forward image %d x %d outside 1..65536 per side", who,
-               f.width, f.height);
-    PX_REQUIRE(f.tanfovx > 0.0f && f.tanfovy > 0.0f, "%s: forward.tanfovx %g, forward.tanfovy %g must be positive", who, f.tanfovx, f.tanfovy);
+    if (check_forward_desc(who, "forward.", f)) return 1;
     PX_REQUIRE(d->instances >= 0 && d->instances <= (int64_t)UINT32_MAX, "%s: instances %lld outside [0, 2^32)", who, (long long)d->instances);
     PX_REQUIRE(f.d_final_T, "%s: null pointer (forward.d_final_T is required: render with it)", who);
     PX_REQUIRE(f.d_n_contrib, "%s: null pointer (forward.d_n_contrib is required: render with it)", who);
-    PX_REQUIRE(f.d_out_color && d->d_dL_dcolor, "%s: null pointer (forward.d_out_color and d_dL_dcolor are required)", who);
+    PX_REQUIRE(d->d_dL_dcolor, "%s: null pointer (d_dL_dcolor is required)", who);
     PX_REQUIRE(!(d->d_dL_dcov3D && (d->d_dL_dscales || d->d_dL_drotations)),
                "%s: give d_dL_dcov3D or the pair d_dL_dscales, d_dL_drotations, as the forward took its covariance, not both", who);
     if (n > 0) {
-        PX_REQUIRE(f.d_means && f.d_colors && f.d_opacity && f.d_radii,
-                   "%s: null pointer (forward.d_means, d_colors, d_opacity and d_radii are required)", who);
-        PX_REQUIRE((f.d_cov3d != nullptr) != (f.d_scales != nullptr || f.d_rotations != nullptr) && (f.d_cov3d || (f.d_scales && f.d_rotations)),
-                   "%s: the forward takes either d_cov3d or the pair d_scales, d_rotations", who);
         PX_REQUIRE(!d->d_dL_dcov3D || f.d_cov3d, "%s: d_dL_dcov3D given, but the forward took d_scales and d_rotations", who);
         PX_REQUIRE(!(d->d_dL_dscales || d->d_dL_drotations) || f.d_scales,
                    "%s: d_dL_dscales / d_dL_drotations given, but the forward took d_cov3d", who);
@@ -261,9 +246,12 @@ int pixie_raster_backward(const pixie_raster_backward_desc* d, void* stream) {
                "%s: d_grad_workspace of %lld bytes is smaller than the %lld bytes that %lld instances need", who,
                (long long)(d->d_grad_workspace ? d->grad_workspace_bytes : 0), (long long)need, (long long)d->instances);
     PX_REQUIRE(((uintptr_t)d->d_grad_workspace & 15) == 0, "%s: d_grad_workspace must be 16-byte aligned", who);
-    if (!(d->d_dL_dmeans3D || d->d_dL_dmeans2D || d->d_dL_dopacity || d->d_dL_dcolors || d->d_dL_dshs || d->d_dL_dcov3D || d->d_dL_dscales ||
-          d->d_dL_drotations))
-        return 0;                          // nothing asked for
+    const struct { float* p; size_t floats; } outs[] = {           // every gradient, with its floats per Gaussian
+        {d->d_dL_dmeans3D, 3}, {d->d_dL_dmeans2D, 3}, {d->d_dL_dopacity, 1}, {d->d_dL_dcolors, 3}, {d->d_dL_dshs, 3 * (size_t)d->sh_k},
+        {d->d_dL_dcov3D, 6}, {d->d_dL_dscales, 3}, {d->d_dL_drotations, 4}};
+    bool asked = false;
+    for (const auto& o : outs) asked = asked || o.p;
+    if (!asked) return 0;                  // nothing asked for
     if (n == 0) return 0;                  // every output is empty
     const rm::Camera cam = rm::make_camera(f.viewmatrix, f.projmatrix, f.tanfovx, f.tanfovy, f.width, f.height);
     const int tiles = cam.tiles_x * cam.tiles_y;
@@ -273,16 +261,9 @@ int pixie_raster_backward(const pixie_raster_backward_desc* d, void* stream) {
                "%s: forward.d_workspace of %lld bytes cannot be the 16-byte aligned workspace of a forward with %lld instances (%lld bytes)", who,
                (long long)f.workspace_bytes, (long long)d->instances, (long long)L.total_bytes);
     hipStream_t st = as_stream(stream);
-    const size_t N = (size_t)n;
     if (d->instances == 0) {
-        if (d->d_dL_dmeans3D) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dmeans3D, 0, sizeof(float) * 3 * N, st));
-        if (d->d_dL_dmeans2D) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dmeans2D, 0, sizeof(float) * 3 * N, st));
-        if (d->d_dL_dopacity) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dopacity, 0, sizeof(float) * N, st));
-        if (d->d_dL_dcolors) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dcolors, 0, sizeof(float) * 3 * N, st));
-        if (d->d_dL_dshs) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dshs, 0, sizeof(float) * 3 * N * (size_t)d->sh_k, st));
-        if (d->d_dL_dcov3D) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dcov3D, 0, sizeof(float) * 6 * N, st));
-        if (d->d_dL_dscales) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_dscales, 0, sizeof(float) * 3 * N, st));
-        if (d->d_dL_drotations) PX_CHECK_HIP(hipMemsetAsync(d->d_dL_drotations, 0, sizeof(float) * 4 * N, st));
+        for (const auto& o : outs)           // nothing was drawn: every gradient asked for is zero
+            if (o.p) PX_CHECK_HIP(hipMemsetAsync(o.p, 0, sizeof(float) * o.floats * (size_t)n, st));
         return 0;
     }
     const char* ws = (const char*)f.d_workspace;

@@ -101,14 +101,30 @@ def convert_SH(shs_view, viewpoint_camera, pc, position, rotation=None):
     return sh_to_rgb(shs_view, int(pc.active_sh_degree), position, viewpoint_camera.camera_center, rotation)
 
 
-class _OwnedWorkspace:
-    """The workspace of one differentiable render: it belongs to that render's autograd node, because the backward reads it as the
-    forward left it and the module's shared workspace is overwritten by the next call."""
+class _Workspace:
+    """A pixie_raster_forward workspace and what it was sized for.  A GaussianRasterizer keeps one between its forward-only calls; a
+    differentiable render gets one of its own, which belongs to that render's autograd node, because the backward reads it as the
+    forward left it and the module's is overwritten by the next call."""
 
     def __init__(self):
         self._workspace = None
-        self._capacity = 0
+        self._capacity = 0             # instances the workspace was sized for
         self._key = None
+
+
+def _one_of_shs_or_colors(shs, colors_precomp):
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')     # the reference's text, as callers may match it
+
+
+def _check_output(t, shape, dtype, device, message):
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError(message)
+
+
+def _to_rgb8(images):
+    """float images with values in [0, 1] as 8 bits: round(clip(255 x, 0, 255))"""
+    return (images.detach().float() * 255.0).clamp(0.0, 255.0).round().to(torch.uint8)
 
 
 def _ensure_workspace(holder, lib, n, W, H, device, instances):
@@ -132,10 +148,9 @@ class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rasterizer, aux, *inputs):
         given = dict(zip(_GRAD_INPUTS, inputs))
-        holder = _OwnedWorkspace()
-        out, radii, final_T, n_contrib, state = rasterizer._render(holder, given["means3D"], given["opacities"], given["shs"],
-                                                                   given["colors_precomp"], given["scales"], given["rotations"],
-                                                                   given["cov3D_precomp"], None, True)
+        out, radii, final_T, n_contrib, state = rasterizer._render(_Workspace(), True, given["means3D"], given["opacities"], given["shs"],
+                                                                   given["colors_precomp"], given["scales"], given["rotations"], given["cov3D_precomp"],
+                                                                   None, True)
         ctx.state = state                      # descriptor, workspace, instance count, SH parameters
         ctx.meta = [None if t is None else (tuple(t.shape), t.dtype) for t in inputs]
         ctx.save_for_backward(out, radii, final_T, n_contrib, *state["tensors"])
@@ -198,16 +213,17 @@ class GaussianRasterizer(torch.nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
         self.raster_settings = raster_settings
-        self._workspace = None
-        self._capacity = 0             # instances the workspace was sized for
-        self._key = None
+        self._ws = _Workspace()        # of the forward-only calls
         self._host = None              # (settings object, viewmatrix, projmatrix, bg as ctypes arrays): read back once per settings
         self.last_instances = 0
         self._owned_hint = (None, 0)   # (shape key, instance capacity) of the last differentiable render
 
+    _workspace = property(lambda self: self._ws._workspace)
+    _capacity = property(lambda self: self._ws._capacity)
+
     def _ensure_workspace(self, lib, n, device, instances):
         s = self.raster_settings
-        _ensure_workspace(self, lib, n, int(s.image_width), int(s.image_height), device, instances)
+        _ensure_workspace(self._ws, lib, n, int(s.image_width), int(s.image_height), device, instances)
 
     def _host_settings(self):
         s = self.raster_settings
@@ -221,8 +237,7 @@ class GaussianRasterizer(torch.nn.Module):
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                 out=None, aux=False):
         s = self.raster_settings
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        _one_of_shs_or_colors(shs, colors_precomp)
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
@@ -230,19 +245,19 @@ class GaussianRasterizer(torch.nn.Module):
         if out is None and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in inputs):
             color, radii, final_T, n_contrib = _Rasterize.apply(self, aux, *inputs)
             return (color, radii, final_T, n_contrib) if aux else (color, radii)
-        res = self._render(self, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux)
+        res = self._render(self._ws, False, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux)
         return res[:4] if aux else res[:2]
 
-    def _render(self, holder, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux):
-        """One pixie_raster_forward on `holder`'s workspace (the module itself, or the _OwnedWorkspace of a differentiable render).
-        Returns (out, radii, final_T, n_contrib, what a backward needs)."""
+    def _render(self, holder, differentiable, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, out, aux):
+        """One pixie_raster_forward on the workspace `holder`: the module's own, or with `differentiable` the one that render's
+        autograd node will own.  Returns (out, radii, final_T, n_contrib, what a backward needs: None unless `differentiable`)."""
         s = self.raster_settings
         means = _device_f32(means3D, "GaussianRasterizer: means3D", (3,))
         n, device = means.shape[0], means.device
         sh = None
         if shs is not None:
             colors = sh_to_rgb(shs, int(s.sh_degree), means, self._host_settings()[4])
-            if holder is not self:
+            if differentiable:
                 sh = _device_f32(shs, "GaussianRasterizer: shs", tuple(shs.shape[1:]), n)
         else:
             colors = _device_f32(colors_precomp, "GaussianRasterizer: colors_precomp", (3,), n)
@@ -256,8 +271,8 @@ class GaussianRasterizer(torch.nn.Module):
         H, W = int(s.image_height), int(s.image_width)
         if out is None:
             out = torch.empty((3, H, W), dtype=torch.float32, device=device)
-        elif out.shape != (3, H, W) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
-            raise ValueError(f"GaussianRasterizer: out must be a contiguous float32 (3, {H}, {W}) tensor on {device}")
+        else:
+            _check_output(out, (3, H, W), torch.float32, device, f"GaussianRasterizer: out must be a contiguous float32 (3, {H}, {W}) tensor on {device}")
         radii = torch.empty((n,), dtype=torch.int32, device=device)
         final_T = torch.empty((H, W), dtype=torch.float32, device=device) if aux else None
         n_contrib = torch.empty((H, W), dtype=torch.int32, device=device) if aux else None
@@ -273,9 +288,9 @@ class GaussianRasterizer(torch.nn.Module):
         d.d_out_color = out.data_ptr()
         count = C.c_int64(0)
         with torch.cuda.device(device):
-            same = self._key == (n, W, H, device)
+            same = self._ws._key == (n, W, H, device)
             guess = self._capacity if same else 4 * n      # a first guess: four tiles per Gaussian
-            if holder is not self and self._owned_hint[0] == (n, W, H, device):
+            if differentiable and self._owned_hint[0] == (n, W, H, device):
                 guess = max(guess, self._owned_hint[1])    # what the last differentiable render of this shape needed
             _ensure_workspace(holder, lib, n, W, H, device, guess)
             for attempt in (0, 1):
@@ -292,7 +307,7 @@ class GaussianRasterizer(torch.nn.Module):
                 holder._capacity = grown
         _lib.check(rc, "pixie_raster_forward", lib=lib)
         self.last_instances = int(count.value)
-        if holder is self:
+        if not differentiable:
             return out, radii, final_T, n_contrib, None
         self._owned_hint = ((n, W, H, device), holder._capacity)
         state = dict(desc=d, instances=int(count.value), n=n, W=W, H=H, workspace=holder._workspace, shs=sh, sh_k=0 if sh is None else int(sh.shape[1]),
@@ -317,8 +332,7 @@ def render_frames(frames, settings_per_frame, opacity, shs=None, colors_precomp=
     pos, cov = frames[0], frames[1]
     if cov is None:
         raise ValueError("render_frames: the frames carry no covariance (FrameSchedule.with_cov)")
-    if (shs is None) == (colors_precomp is None):
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    _one_of_shs_or_colors(shs, colors_precomp)
     n_frames = int(pos.shape[0])
     per_frame = None if isinstance(settings_per_frame, GaussianRasterizationSettings) else list(settings_per_frame)
     if per_frame is not None and len(per_frame) != n_frames:
@@ -450,8 +464,7 @@ class FrameBatchRasterizer:
         (N + M, K, 3) and `colors_precomp` ((N + M, 3) shared, or (V, N + M, 3)).  `out`: a (V, 3, H, W) float32 tensor to fill, None
         to allocate one, False for none; `out_rgb8`: a (V, H, W, 3) uint8 tensor, True to allocate one, None for none.
         `capacity`: the instance capacity of one sort, instead of the rasteriser's own guess.  Returns a FrameBatchOutput."""
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        _one_of_shs_or_colors(shs, colors_precomp)
         if not torch.is_tensor(means) or not torch.is_tensor(cov3D) or means.dim() != 3:
             raise ValueError("FrameBatchRasterizer: means3D and cov3D must be (views, N, 3) and (views, N, 6) tensors")
         V, n_dyn = int(means.shape[0]), int(means.shape[1])
@@ -490,14 +503,16 @@ class FrameBatchRasterizer:
             out = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
         elif out is None or out is False:
             out = None
-        elif out.shape != (V, 3, H, W) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
-            raise ValueError(f"FrameBatchRasterizer: out must be a contiguous float32 ({V}, 3, {H}, {W}) tensor on {device}")
+        else:
+            _check_output(out, (V, 3, H, W), torch.float32, device,
+                          f"FrameBatchRasterizer: out must be a contiguous float32 ({V}, 3, {H}, {W}) tensor on {device}")
         if out_rgb8 is True:
             out_rgb8 = torch.empty((V, H, W, 3), dtype=torch.uint8, device=device)
         elif out_rgb8 is None or out_rgb8 is False:
             out_rgb8 = None
-        elif out_rgb8.shape != (V, H, W, 3) or out_rgb8.dtype != torch.uint8 or out_rgb8.device != device or not out_rgb8.is_contiguous():
-            raise ValueError(f"FrameBatchRasterizer: out_rgb8 must be a contiguous uint8 ({V}, {H}, {W}, 3) tensor on {device}")
+        else:
+            _check_output(out_rgb8, (V, H, W, 3), torch.uint8, device,
+                          f"FrameBatchRasterizer: out_rgb8 must be a contiguous uint8 ({V}, {H}, {W}, 3) tensor on {device}")
         radii = torch.empty((V, n), dtype=torch.int32, device=device)
         final_T = torch.empty((V, H, W), dtype=torch.float32, device=device) if aux else None
         n_contrib = torch.empty((V, H, W), dtype=torch.int32, device=device) if aux else None
@@ -555,8 +570,7 @@ def render_frame_batch(frames, settings_per_frame, opacity, shs=None, colors_pre
     pos, cov = frames[0], frames[1]
     if cov is None:
         raise ValueError("render_frame_batch: the frames carry no covariance (FrameSchedule.with_cov)")
-    if (shs is None) == (colors_precomp is None):
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    _one_of_shs_or_colors(shs, colors_precomp)
     n_frames = int(pos.shape[0])
     per_frame = [settings_per_frame] * n_frames if isinstance(settings_per_frame, GaussianRasterizationSettings) else list(settings_per_frame)
     if len(per_frame) != n_frames:
@@ -574,8 +588,8 @@ def render_frame_batch(frames, settings_per_frame, opacity, shs=None, colors_pre
     elif out_rgb8 is False:
         out_rgb8 = None
     for t, shape, dtype in ((out, (n_frames, 3, H, W), torch.float32), (out_rgb8, (n_frames, H, W, 3), torch.uint8)):
-        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != pos.device or not t.is_contiguous()):
-            raise ValueError(f"render_frame_batch: an output must be a contiguous {dtype} {shape} tensor on {pos.device}")
+        if t is not None:
+            _check_output(t, shape, dtype, pos.device, f"render_frame_batch: an output must be a contiguous {dtype} {shape} tensor on {pos.device}")
     r = rasterizer if rasterizer is not None else FrameBatchRasterizer()
     n = int(pos.shape[1]) + (0 if unselected is None else int(unselected[0].shape[0]))
     step = int(frames_per_call) if frames_per_call else _default_frames_per_call(n, n_frames, r.max_workspace_bytes)
@@ -602,7 +616,7 @@ def save_frame_png(path, image):
         from PIL import Image
     except ImportError as exc:
         raise RuntimeError("save_frame_png needs Pillow (PIL), which is not installed") from exc
-    a = (image.detach().float() * 255.0).clamp(0.0, 255.0).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
+    a = _to_rgb8(image).permute(1, 2, 0).contiguous().cpu().numpy()
     Image.fromarray(a).save(path, format="PNG")
     return path
 
@@ -619,7 +633,7 @@ def save_frame_pngs(dir, rgb8_or_images, start=0):
     except ImportError as exc:
         raise RuntimeError("save_frame_png needs Pillow (PIL), which is not installed") from exc
     if t.dtype != torch.uint8:
-        t = (t.detach().float() * 255.0).clamp(0.0, 255.0).round().to(torch.uint8).permute(0, 2, 3, 1)
+        t = _to_rgb8(t).permute(0, 2, 3, 1)
     a = t.detach().contiguous().cpu().numpy()
     os.makedirs(dir, exist_ok=True)
     paths = []

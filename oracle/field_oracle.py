@@ -3,15 +3,17 @@ TEST INFRASTRUCTURE ONLY: only tests/, __graft_entry__.smoke() and bench.py's cp
 
 Follows, function by function (paths relative to /root/reference):
   unscale_prediction     pixie/voxel/map_pred_to_coords.py:41-75   (clip to [-1,1], 10**log ranges)
-  voxel_point_cloud      pixie/voxel/map_pred_to_coords.py:192-252 (np.linspace coordinates, mask > 0, argmax id, max conf;
-                          the PLY stores x,y,z,density,E,nu,conf as 'f4' and the ids as 'i4')
+  voxel_point_cloud      pixie/voxel/map_pred_to_coords.py:192-252 (np.linspace coordinates, mask > 0, get_mat_id :122-126 -- argmax
+                          id and max conf, or a single class channel taken as the id itself with conf 1; the PLY stores
+                          x,y,z,density,E,nu,conf as 'f4' and the ids as 'i4')
   knn_assign             third_party/PhysGaussian/material_field.py:228-300 (sklearn NearestNeighbors, K = 10, too-far test
                           on the nearest distance only) with MaterialProperties.get_defaults (:38-50) and
                           .assign_from_neighbors (:52-78: np.mean / Counter.most_common, or inverse-distance weights)
 Pinned: tests/golden/field_transfer.npz is produced by tests/golden/make_field_golden.py, which executes the
 reference's own unscale_prediction and MaterialProperties source (extracted from the files above with `ast`, because
 their modules import hydra / warp / plyfile, which are not installed) -- tests/test_field_oracle.py checks this
-restatement against it bit for bit.
+restatement against it bit for bit.  tests/golden/field_edges.npz (make_field_edge_golden.py, the same way) pins the edges:
+other range sets, NaN / inf / clip-edge inputs, and a prediction with one class channel.
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ def unscale_prediction(pred: np.ndarray, ranges=NORMALIZATION_RANGES) -> np.ndar
 def voxel_point_cloud(pred_unscaled: np.ndarray, mask: np.ndarray, min_bounds, max_bounds):
     """map_pred_to_coords.py:192-252 -> dict of the PLY vertex columns (float32 / int32)."""
     cont, seg = pred_unscaled[:3], pred_unscaled[3:]
-    material_id = np.argmax(seg, axis=0)
+    material_id = seg[0] if seg.shape[0] == 1 else np.argmax(seg, axis=0)   # get_mat_id: one class channel IS the class index
     D, H, W = mask.shape
     x = np.linspace(min_bounds[0], max_bounds[0], D)
     y = np.linspace(min_bounds[1], max_bounds[1], H)
@@ -52,7 +54,7 @@ def voxel_point_cloud(pred_unscaled: np.ndarray, mask: np.ndarray, min_bounds, m
     valid = mask > 0
     pos = np.stack([gx[valid], gy[valid], gz[valid]], axis=-1).astype(np.float32)
     conf = np.max(seg, axis=0)[valid].astype(np.float32) if seg.shape[0] > 1 else np.ones(int(valid.sum()), np.float32)
-    mid = material_id[valid].astype(np.int32)
+    mid = material_id[valid].astype(np.int32)                               # (the 'i4' column truncates the float ids)
     return dict(pos=pos, density=cont[0][valid].astype(np.float32), E=cont[1][valid].astype(np.float32),
                 nu=cont[2][valid].astype(np.float32), material_id=mid, part_labels=mid.copy(), conf=conf)
 

@@ -27,7 +27,10 @@ struct FieldArgs {
     const float* ax; const float* ay; const float* az;   // voxel coordinates per axis (float32(np.linspace))
     int ncls, D, H, W;
     double hmin;                // smallest lattice spacing
-    float dmin, dmax, emin, emax, numin, numax;  // log10 density / log10 E / nu ranges
+    // log10 density / log10 E / nu ranges as the reference's float32 array arithmetic sees them: lo = float32(min), and
+    // span = float32(max - min) with the difference taken in float64 ON THE HOST (field_ranges below) and rounded once --
+    // NOT float32(max) - float32(min), which is up to 4.5e-6 relative away in E for ranges that float32 does not hold exactly
+    float dmin, dspan, emin, espan, numin, nuspan;
     const float* pos; int n;    // particles [n][3], in the field's frame
     int k; double thr; int weighted;
     int def_material, def_label;
@@ -36,20 +39,17 @@ struct FieldArgs {
     unsigned long long* n_far;
 };
 
-__device__ __forceinline__ float unscale_log(float c, float lo, float hi) {
-    c = fminf(fmaxf(c, -1.0f), 1.0f);
-    const float l = (c + 1.0f) * (hi - lo) / 2.0f + lo;   // float32 arithmetic, as numpy does on the float32 array
-    return powf(10.0f, l);
+// np.clip(c, -1, 1): +-inf go to the ends, NaN stays NaN (fminf / fmaxf would return the other operand, i.e. -1)
+__device__ __forceinline__ float clip_unit(float c) { return c < -1.0f ? -1.0f : (c > 1.0f ? 1.0f : c); }
+__device__ __forceinline__ float unscale_lin(float c, float lo, float span) {
+    return (clip_unit(c) + 1.0f) * span / 2.0f + lo;      // float32 arithmetic, as numpy does on the float32 array
 }
-__device__ __forceinline__ float unscale_lin(float c, float lo, float hi) {
-    c = fminf(fmaxf(c, -1.0f), 1.0f);
-    return (c + 1.0f) * (hi - lo) / 2.0f + lo;
-}
+__device__ __forceinline__ float unscale_log(float c, float lo, float span) { return powf(10.0f, unscale_lin(c, lo, span)); }
 __device__ __forceinline__ void voxel_props(const FieldArgs& A, long v, float& dens, float& e, float& nu, int& mid, float& conf) {
     const long S = (long)A.D * A.H * A.W;
-    dens = unscale_log(A.pred[v], A.dmin, A.dmax);
-    e = unscale_log(A.pred[S + v], A.emin, A.emax);
-    nu = unscale_lin(A.pred[2 * S + v], A.numin, A.numax);
+    dens = unscale_log(A.pred[v], A.dmin, A.dspan);
+    e = unscale_log(A.pred[S + v], A.emin, A.espan);
+    nu = unscale_lin(A.pred[2 * S + v], A.numin, A.nuspan);
     mid = 0;
     conf = A.pred[3 * S + v];
     for (int c = 1; c < A.ncls; ++c) {   // np.argmax: first maximum
@@ -191,12 +191,12 @@ __global__ __launch_bounds__(128) void field_knn_kernel(FieldArgs A) {
 // unscale_prediction (pixie/voxel/map_pred_to_coords.py:41-75): channels 0..2 clipped to [-1, 1] and mapped back to
 // 10^log-range (density, E) / the linear range (nu); the class channels are copied.
 __global__ __launch_bounds__(256) void unscale_kernel(const float* __restrict__ pred, float* __restrict__ out, int channels, long S,
-                                                      float dmin, float dmax, float emin, float emax, float numin, float numax) {
+                                                      float dmin, float dspan, float emin, float espan, float numin, float nuspan) {
     const long v = (long)blockIdx.x * 256 + threadIdx.x;
     if (v >= S) return;
-    out[v] = unscale_log(pred[v], dmin, dmax);
-    out[S + v] = unscale_log(pred[S + v], emin, emax);
-    out[2 * S + v] = unscale_lin(pred[2 * S + v], numin, numax);
+    out[v] = unscale_log(pred[v], dmin, dspan);
+    out[S + v] = unscale_log(pred[S + v], emin, espan);
+    out[2 * S + v] = unscale_lin(pred[2 * S + v], numin, nuspan);
     for (int c = 3; c < channels; ++c) out[(long)c * S + v] = pred[(long)c * S + v];
 }
 
@@ -252,6 +252,13 @@ __global__ __launch_bounds__(kPtsWG) void points_write_kernel(FieldArgs A, const
     dens[slot] = d; E[slot] = e; nu[slot] = n; material[slot] = mid; conf[slot] = cf;
 }
 
+// the ranges of a pixie_field_desc (doubles) as the kernels use them: see FieldArgs
+static void field_ranges(FieldArgs& A, const pixie_field_desc* f) {
+    A.dmin = (float)f->density_min; A.dspan = (float)(f->density_max - f->density_min);
+    A.emin = (float)f->E_min; A.espan = (float)(f->E_max - f->E_min);
+    A.numin = (float)f->nu_min; A.nuspan = (float)(f->nu_max - f->nu_min);
+}
+
 }  // namespace pixie
 
 using namespace pixie;
@@ -260,7 +267,8 @@ extern "C" int pixie_unscale_prediction(const float* d_pred, int channels, int64
                                         double E_min, double E_max, double nu_min, double nu_max, float* d_out, void* stream) {
     PX_REQUIRE(d_pred && d_out && channels >= 3 && spatial > 0, "pixie_unscale_prediction: bad arguments");
     hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)((spatial + 255) / 256)), dim3(256), 0, as_stream(stream), d_pred, d_out, channels,
-                       (long)spatial, (float)density_min, (float)density_max, (float)E_min, (float)E_max, (float)nu_min, (float)nu_max);
+                       (long)spatial, (float)density_min, (float)(density_max - density_min), (float)E_min, (float)(E_max - E_min), (float)nu_min,
+                       (float)(nu_max - nu_min));   // spans: float64 difference rounded once, as FieldArgs
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -281,8 +289,7 @@ extern "C" int pixie_field_points(const pixie_field_desc* f, int64_t capacity, f
     FieldArgs A{};
     A.pred = f->d_pred; A.mask = f->d_mask; A.ax = f->d_axis_x; A.ay = f->d_axis_y; A.az = f->d_axis_z;
     A.ncls = f->n_classes; A.D = f->d; A.H = f->h; A.W = f->w;
-    A.dmin = (float)f->density_min; A.dmax = (float)f->density_max; A.emin = (float)f->E_min; A.emax = (float)f->E_max;
-    A.numin = (float)f->nu_min; A.numax = (float)f->nu_max;
+    field_ranges(A, f);
     const long S = (long)A.D * A.H * A.W;
     PX_REQUIRE(S < (1l << 31), "pixie_field_points: grid too large");
     const int nblocks = (int)((S + kPtsWG - 1) / kPtsWG);
@@ -310,8 +317,7 @@ extern "C" int pixie_field_to_particles(const pixie_field_desc* f, const float* 
     A.pred = f->d_pred; A.mask = f->d_mask; A.ax = f->d_axis_x; A.ay = f->d_axis_y; A.az = f->d_axis_z;
     A.ncls = f->n_classes; A.D = f->d; A.H = f->h; A.W = f->w;
     A.hmin = f->min_spacing;
-    A.dmin = (float)f->density_min; A.dmax = (float)f->density_max; A.emin = (float)f->E_min; A.emax = (float)f->E_max;
-    A.numin = (float)f->nu_min; A.numax = (float)f->nu_max;
+    field_ranges(A, f);
     A.pos = d_pos; A.n = n; A.k = k; A.thr = nn_distance_threshold; A.weighted = weighted;
     A.def_material = default_material; A.def_label = default_part_label;
     double* sums = static_cast<double*>(d_scratch);               // [5] doubles, then the too-far counter

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import field_oracle
+from tests._field_parity import compare
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "field_transfer.npz")
@@ -18,16 +19,6 @@ def run_hip(dev, pred, mask, lo, hi, pos, **kw):
     from pixie_amd.material_field import field_to_particles
     out = field_to_particles(torch.from_numpy(pred).to(dev), torch.from_numpy(mask).to(dev), lo, hi, torch.from_numpy(pos).to(dev), **kw)
     return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def compare(got, ref, too_far):
-    assert int(got["n_too_far"]) == int(too_far.sum())
-    for key in ("material_id", "part_labels"):
-        assert np.array_equal(got[key], ref[key]), key
-    for key in ("density", "E", "nu", "conf"):
-        rel = np.abs(got[key].astype(np.float64) - ref[key]) / np.maximum(np.abs(ref[key]), 1e-30)
-        assert rel.max() < 2e-6, (key, rel.max())
-    assert np.abs(got["nearest_dist"] - ref["nearest_dist"]).max() < 1e-6
 
 
 @pytest.mark.parametrize("weighted", [False, True])
@@ -40,15 +31,16 @@ def test_matches_reference_golden(hip_device, weighted):
     compare(got, ref, g[tag + "too_far"])
 
 
+@pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("D,n,k", [(32, 20000, 10), (16, 500, 1), (20, 3000, 16)])
-def test_matches_oracle_on_other_shapes(hip_device, D, n, k):
+def test_matches_oracle_on_other_shapes(hip_device, D, n, k, weighted):
     rng = np.random.default_rng(D + n)
     pred = rng.normal(0, 0.6, size=(11, D, D + 2, D - 3)).astype(np.float32)
     mask = (rng.random((D, D + 2, D - 3)) < 0.5).astype(np.float32)       # sparse, anisotropic lattice
     lo, hi = np.array([0.0, -1.0, 2.0]), np.array([1.5, 1.0, 3.0])
     pos = (lo + (hi - lo) * rng.random((n, 3)) * 1.1 - 0.05 * (hi - lo)).astype(np.float32)  # some outside the lattice
-    got = run_hip(hip_device, pred, mask, lo, hi, pos, k=k, nn_distance_threshold=0.08)
-    ref = field_oracle.field_to_particles(pred, mask, lo, hi, pos, k=k, nn_distance_threshold=0.08)
+    got = run_hip(hip_device, pred, mask, lo, hi, pos, k=k, nn_distance_threshold=0.08, weighted=weighted)
+    ref = field_oracle.field_to_particles(pred, mask, lo, hi, pos, k=k, nn_distance_threshold=0.08, weighted=weighted)
     compare(got, ref, ref["too_far"])
 
 

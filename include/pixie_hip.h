@@ -672,6 +672,33 @@ int64_t pixie_scene_ingest_workspace_bytes(int64_t n);
  * Deterministic: the same input gives the same bits. */
 int pixie_scene_ingest(const pixie_ingest_desc* desc, int64_t counts_out[3], float scale_out[1], float mean_out[3], void* stream);
 
+/* ---- 3DGS training natives: what gaussian-splatting/train.py needs beside its rasteriser ---- */
+
+/* distCUDA2 of simple-knn (scene/gaussian_model.py:20, :134): d_out[i] = ((b0 + b1) + b2) / 3 with b0 <= b1 <= b2 the three
+ * smallest ((dx dx + dy dy) + dz dz) over all OTHER points j != i (by index: a coincident point counts at distance 0), float32,
+ * no fused multiply-add.  A missing neighbour counts as FLT_MAX, as in the reference: one or two points give +inf, three give
+ * FLT_MAX / 3.  The search is exact, so the result is bit-equal to a float32 brute force in that expression order, bit-identical
+ * from run to run and independent of the order of the rows.  The coordinates must be finite; a NaN gives unspecified values for
+ * the affected points and nothing worse.  d_points [n][3], d_out [n]: caller-owned device memory; d_scratch: 16-byte aligned,
+ * pixie_knn_mean_dist2_scratch_bytes(n) bytes (-1 for n outside [0, 2^24]).  n above 2^24 and a scratch buffer that is too small
+ * are refused before anything is launched; n = 0 launches nothing.  Asynchronous on `stream`. */
+int64_t pixie_knn_mean_dist2_scratch_bytes(int64_t n);
+int pixie_knn_mean_dist2(const float* d_points, int64_t n, void* d_scratch, int64_t scratch_bytes, float* d_out, void* stream);
+
+/* l1_loss and ssim of utils/loss_utils.py (window 11, sigma 1.5, zero padding 5, one window per channel, C1 = 1e-4, C2 = 9e-4) of
+ * d_img against d_gt, both [b][c][h][w] float32, as per-image means d_out_l1[b] and d_out_ssim[b]: one fused launch and a
+ * one-workgroup-per-image finalise, no floating-point atomics (bit-identical from run to run), no synchronise.  The window is
+ * applied separably.  With with_grad != 0 the forward also leaves three planes in the workspace, from which
+ * pixie_photometric_backward writes d_grad_img = sum over the image's two means of g * d mean / d d_img in one launch
+ * (d_g_l1[b], d_g_ssim[b]: the upstream gradients of the means; sign(0) = 0 in the L1 term).  d_workspace: 16-byte aligned,
+ * pixie_photometric_workspace_bytes(...) bytes for the same sizes and with_grad (-1 on error), untouched between the forward and
+ * its backward.  h, w <= 32768 and b * c <= 65535. */
+int64_t pixie_photometric_workspace_bytes(int b, int c, int h, int w, int with_grad);
+int pixie_photometric_forward(const float* d_img, const float* d_gt, int b, int c, int h, int w, void* d_workspace,
+                              int64_t workspace_bytes, int with_grad, float* d_out_l1, float* d_out_ssim, void* stream);
+int pixie_photometric_backward(const float* d_img, const float* d_gt, int b, int c, int h, int w, const void* d_workspace,
+                               const float* d_g_l1, const float* d_g_ssim, float* d_grad_img, void* stream);
+
 /* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)

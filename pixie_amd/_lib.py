@@ -224,6 +224,11 @@ SIGNATURES = {
     "pixie_scene_ingest_workspace_bytes": (_I64, [_I64]),
     "pixie_scene_ingest": (_I, [C.POINTER(IngestDesc), C.POINTER(_I64), C.POINTER(C.c_float), C.POINTER(C.c_float), _VP]),
     "pixie_field_to_particles": (_I, [C.POINTER(FieldDesc), _VP, _I, _I, _D, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pixie_knn_mean_dist2_scratch_bytes": (_I64, [_I64]),
+    "pixie_knn_mean_dist2": (_I, [_VP, _I64, _VP, _I64, _VP, _VP]),
+    "pixie_photometric_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "pixie_photometric_forward": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _I64, _I, _VP, _VP, _VP]),
+    "pixie_photometric_backward": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
 }
 
 # entry points that exist only in the PIXIE_DIAG build (include/pixie_hip.h, last section)

@@ -203,12 +203,19 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     const float* wF = A.wf + (size_t)kh * A.coutp + cout0 + l31;     // EX: channel (2 kp + kh) of the pair, row l31 of block mb
 
     constexpr int TAPS = KS * KS * KS;
-    // ---- stage the 16-channel chunk starting at c_base into `buf`: one voxel x 16 channels per item, two items per
-    // thread in flight.  Everything uniform is kept out of the per-element code: the channel base pointers are scalar,
+    // ---- stage the 16-channel chunk starting at c_base into `buf`: one voxel x 16 channels per item.  A thread owns the items
+    // k = 0 .. n - 1 at slots stid + nthr k, n = ceil(CS / nthr) (workgroup-uniform; 5 at the 34 x 6 x 6 tile), and walks them as a
+    // rotating pipeline over two register sets: the 16 + 2 loads of item k + 1 are issued -- behind its geometry, which is computed
+    // under the flight of item k -- before item k is converted and written, so a chunk exposes ONE global-memory round trip and
+    // every later conversion waits with a counted vmcnt while the younger item is in flight.  The loop is unrolled by two so that
+    // neither set is ever copied, and the last one or two items are peeled: a load behind a branch would make the wait in front
+    // of the older item a full one.  (Before: passes of two items per thread, each pass load -> wait -> convert -> store, three
+    // exposed round trips at that tile and 1536 item slots for 1224; profiles/conv_staging_pricing.txt.)
+    // Everything uniform is kept out of the per-element code: the channel base pointers are scalar,
     // the 32 per-channel prologue constants are fetched with ONE vector load per wave and broadcast into SGPRs with
-    // v_readlane, out-of-range voxels load element 0 (masked after the activation) so the 32 + 4 loads of an item pair
+    // v_readlane, out-of-range voxels load element 0 (masked after the activation) so the 16 + 2 loads of an item
     // issue back to back without exec-mask branches, and the (has-prologue, activation) switch selects one of six
-    // straight-line conversion bodies.  (The first version left those decisions to per-element code; the compiler
+    // straight-line pipelines.  (The first version left those decisions to per-element code; the compiler
     // turned the constants into dependent vector loads with s_waitcnt vmcnt(0) -- 16 of the 27 us a chunk took.)
     auto stage_chunk = [&](int c_base, uint4* buf, int stid, int nthr) {
         uint4* bHi = buf;
@@ -224,40 +231,43 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             }
         }
         const bool has_aff = A.gamma != nullptr;
-        for (int v0 = stid; v0 < A.CS; v0 += 2 * nthr) {
-            float val[2][16];
-            float gm[2], bt[2];
-            int sidx[2];
-            bool ok[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int vox = v0 + u * nthr;
-                int rem = vox;
-                const int hz = fast_div16(rem, A.HYX, A.mHYX);
-                rem -= hz * A.HYX;
-                const int hy = fast_div16(rem, A.HX, A.mHX);
-                const int hx = rem - hy * A.HX;
-                const int lz = lz0 + hz, ly = ly0 + hy, lx = lx0 + hx;
-                ok[u] = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
-                sidx[u] = ok[u] ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int cg = c_base + j;
-                    const float* src = (cg < A.c0) ? (A.in0 + (size_t)cg * ISP) : (A.in1 + (size_t)(cg - A.c0) * ISP);
-                    val[u][j] = src[sidx[u]];
-                }
-                gm[u] = 1.0f; bt[u] = 0.0f;
-                if (has_aff) { gm[u] = A.gamma[sidx[u]]; bt[u] = A.beta[sidx[u]]; }
-            }
-            auto convert = [&](auto has_pro, auto act_c) {
+        using T = std::true_type; using F = std::false_type;
+        if constexpr (EX) {
+            // the exact-fp32 body keeps the two-items-per-pass loop: the pipeline below costs it registers (<3,2,4>: 243 -> 256
+            // VGPRs and spills, <3,2,2>: occupancy 3 -> 2; profiles/conv_staging_kernel_resources_after.txt has the f16x3 side)
+            float* bF = reinterpret_cast<float*>(buf);
+            for (int v0 = stid; v0 < A.CS; v0 += 2 * nthr) {
+                float val[2][16];
+                float gm[2], bt[2];
+                int sidx[2];
+                bool ok[2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const int vox = v0 + u * nthr;
-                    if (EX) {
-                        float* bF = reinterpret_cast<float*>(buf);
+                    int rem = vox;
+                    const int hz = fast_div16(rem, A.HYX, A.mHYX);
+                    rem -= hz * A.HYX;
+                    const int hy = fast_div16(rem, A.HX, A.mHX);
+                    const int hx = rem - hy * A.HX;
+                    const int lz = lz0 + hz, ly = ly0 + hy, lx = lx0 + hx;
+                    ok[u] = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
+                    sidx[u] = ok[u] ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
+                }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const int cg = c_base + j;
+                        const float* src = (cg < A.c0) ? (A.in0 + (size_t)cg * ISP) : (A.in1 + (size_t)(cg - A.c0) * ISP);
+                        val[u][j] = src[sidx[u]];
+                    }
+                    gm[u] = 1.0f; bt[u] = 0.0f;
+                    if (has_aff) { gm[u] = A.gamma[sidx[u]]; bt[u] = A.beta[sidx[u]]; }
+                }
+                auto convert = [&](auto has_pro, auto act_c) {
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int vox = v0 + u * nthr;
 #pragma unroll
                         for (int j = 0; j < 16; ++j) {
                             float t = val[u][j];
@@ -266,37 +276,99 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
                             const float sc = ok[u] ? act16(t, decltype(act_c)::value) : 0.0f;   // zero padding AFTER the activation
                             if (vox < A.CS) bF[j * A.CS + vox] = sc;
                         }
-                        continue;
                     }
-                    f16x8 vh[2], vl[2];
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        float t = val[u][j];
-                        if (decltype(has_pro)::value) t = t * pa[j] + pb[j];
-                        t = t * gm[u] + bt[u];
-                        const float sc = ok[u] ? act16(t, decltype(act_c)::value) * sx : 0.0f;   // zero padding AFTER the activation
-                        const _Float16 h = (_Float16)sc;
-                        vh[j >> 3][j & 7] = h;
-                        vl[j >> 3][j & 7] = (_Float16)(sc - (float)h);
-                    }
-                    if (vox < A.CS) {
-                        bHi[vox] = __builtin_bit_cast(uint4, vh[0]);
-                        bHi[A.CS + vox] = __builtin_bit_cast(uint4, vh[1]);
-                        bLo[vox] = __builtin_bit_cast(uint4, vl[0]);
-                        bLo[A.CS + vox] = __builtin_bit_cast(uint4, vl[1]);
-                    }
+                };
+                if (A.pro_a) {
+                    if (A.act == 1) convert(T{}, std::integral_constant<int, 1>{});
+                    else if (A.act == 2) convert(T{}, std::integral_constant<int, 2>{});
+                    else convert(T{}, std::integral_constant<int, 0>{});
+                } else {
+                    if (A.act == 1) convert(F{}, std::integral_constant<int, 1>{});
+                    else if (A.act == 2) convert(F{}, std::integral_constant<int, 2>{});
+                    else convert(F{}, std::integral_constant<int, 0>{});
                 }
-            };
-            using T = std::true_type; using F = std::false_type;
-            if (A.pro_a) {
-                if (A.act == 1) convert(T{}, std::integral_constant<int, 1>{});
-                else if (A.act == 2) convert(T{}, std::integral_constant<int, 2>{});
-                else convert(T{}, std::integral_constant<int, 0>{});
-            } else {
-                if (A.act == 1) convert(F{}, std::integral_constant<int, 1>{});
-                else if (A.act == 2) convert(F{}, std::integral_constant<int, 2>{});
-                else convert(F{}, std::integral_constant<int, 0>{});
             }
+            return;
+        }
+        const int n_items = (A.CS + nthr - 1) / nthr;
+        // The LayerNorm affine is fetched FIRST and without a branch (no affine: any readable element, replaced by 1 and 0 in the
+        // conversion): every element's conversion needs it, and a load that may or may not have been issued behind the older
+        // item's would turn that item's counted wait into one that also drains the head of the younger.  Without an affine the two
+        // loads read in0[sidx] (in0 is never null and holds c0 >= 1 channels of ISP elements, so the index is in range) and are
+        // discarded: 18 loads per item where the old loop issued 16.  That cost is not priced on its own; the launches without an
+        // affine (sub-pixel up-convs, 1x1x1, stride 2) are in profiles/conv_staging_{before,after}_kernel_stats_by_geometry.csv.
+        const float* gsrc = has_aff ? A.gamma : A.in0;
+        const float* bsrc = has_aff ? A.beta : A.in0;
+        struct Item { float val[16]; float gm, bt; bool ok; };
+        // geometry of the item at slot `vox`, then its loads; nothing here waits for memory
+        auto fetch = [&](Item& it, int vox) {
+            int rem = vox;
+            const int hz = fast_div16(rem, A.HYX, A.mHYX);
+            rem -= hz * A.HYX;
+            const int hy = fast_div16(rem, A.HX, A.mHX);
+            const int hx = rem - hy * A.HX;
+            const int lz = lz0 + hz, ly = ly0 + hy, lx = lx0 + hx;
+            it.ok = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
+            const int sidx = it.ok ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
+            it.gm = gsrc[sidx]; it.bt = bsrc[sidx];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int cg = c_base + j;
+                const float* src = (cg < A.c0) ? (A.in0 + (size_t)cg * ISP) : (A.in1 + (size_t)(cg - A.c0) * ISP);
+                it.val[j] = src[sidx];
+            }
+            // keep these loads above the conversion of the item before: left alone, the scheduler sinks them to their first use
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto convert = [&](const Item& it, int vox, auto has_pro, auto act_c) {
+            const float gm = has_aff ? it.gm : 1.0f, bt = has_aff ? it.bt : 0.0f;
+            f16x8 vh[2], vl[2];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                float t = it.val[j];
+                if (decltype(has_pro)::value) t = t * pa[j] + pb[j];
+                t = t * gm + bt;
+                const float sc = it.ok ? act16(t, decltype(act_c)::value) * sx : 0.0f;   // zero padding AFTER the activation
+                const _Float16 h = (_Float16)sc;
+                vh[j >> 3][j & 7] = h;
+                vl[j >> 3][j & 7] = (_Float16)(sc - (float)h);
+            }
+            if (vox < A.CS) {
+                bHi[vox] = __builtin_bit_cast(uint4, vh[0]);
+                bHi[A.CS + vox] = __builtin_bit_cast(uint4, vh[1]);
+                bLo[vox] = __builtin_bit_cast(uint4, vl[0]);
+                bLo[A.CS + vox] = __builtin_bit_cast(uint4, vl[1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the next fetch reuses this set: it stays below
+        };
+        auto pipeline = [&](auto has_pro, auto act_c) {
+            Item a, b;
+            int vox = stid;              // slot of the item in `a`; the one in `b` is nthr further on
+            int left = n_items;          // items not yet converted, a's included
+            fetch(a, vox);
+#pragma unroll 1
+            for (; left > 2; left -= 2, vox += 2 * nthr) {
+                fetch(b, vox + nthr);
+                convert(a, vox, has_pro, act_c);
+                fetch(a, vox + 2 * nthr);
+                convert(b, vox + nthr, has_pro, act_c);
+            }
+            if (left == 2) {
+                fetch(b, vox + nthr);
+                convert(a, vox, has_pro, act_c);
+                convert(b, vox + nthr, has_pro, act_c);
+            } else {
+                convert(a, vox, has_pro, act_c);
+            }
+        };
+        if (A.pro_a) {
+            if (A.act == 1) pipeline(T{}, std::integral_constant<int, 1>{});
+            else if (A.act == 2) pipeline(T{}, std::integral_constant<int, 2>{});
+            else pipeline(T{}, std::integral_constant<int, 0>{});
+        } else {
+            if (A.act == 1) pipeline(F{}, std::integral_constant<int, 1>{});
+            else if (A.act == 2) pipeline(F{}, std::integral_constant<int, 2>{});
+            else pipeline(F{}, std::integral_constant<int, 0>{});
         }
     };
     // ---- MFMA over the taps of one chunk; the A fragments of tap t+1 are fetched during tap t ----

@@ -699,6 +699,82 @@ int pixie_photometric_forward(const float* d_img, const float* d_gt, int b, int 
 int pixie_photometric_backward(const float* d_img, const float* d_gt, int b, int c, int h, int w, const void* d_workspace,
                                const float* d_g_l1, const float* d_g_ssim, float* d_grad_img, void* stream);
 
+/* ---- 3DGS training natives: what train.py does with the gradients (optimiser step, densification) ---- */
+
+/* torch.optim.Adam (no weight decay, no amsgrad, not maximize) over up to 8 one-tensor groups in ONE launch.  Per element, in
+ * float32 and in this order (no fused multiply-add), the scalars rounded from double: m = m + (1 - beta1) (g - m); v = v beta2 + ((1 - beta2) g) g;
+ * p = p - step_size (m / (sqrt(v) / bias_correction2_sqrt + eps)).  The caller computes step_size = lr / (1 - beta1^t) and
+ * bias_correction2_sqrt = sqrt(1 - beta2^t) in double and rounds once.  param, exp_avg and exp_avg_sq are updated in place; all
+ * four arrays hold `count` floats of caller-owned device memory.  count == 0 is legal (its pointers are not read).  Every element
+ * is updated (dense semantics).  No atomics, no synchronise: bit-identical from run to run. */
+typedef struct pixie_gs_adam_group {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t count;
+    float step_size, bias_correction2_sqrt;
+} pixie_gs_adam_group;
+typedef struct pixie_gs_adam_desc {
+    double beta1, beta2, eps;          /* as Python holds them: 1 - beta is taken in double and rounded once, as torch does */
+    int32_t n_groups;                  /* 0..8 */
+    int32_t pad_;
+    pixie_gs_adam_group group[8];
+} pixie_gs_adam_desc;
+int pixie_gs_adam_step(const pixie_gs_adam_desc* desc, void* stream);
+
+/* train.py:114-116 in one launch, no synchronise: for every i < n with d_radii[i] > 0, d_max_radii2D[i] = max(d_max_radii2D[i],
+ * d_radii[i]); d_xyz_gradient_accum[i] += sqrt(gx gx + gy gy) of d_viewspace_grad [n][3]; d_denom[i] += 1. */
+int pixie_gs_densify_stats(const int32_t* d_radii, const float* d_viewspace_grad, int64_t n, float* d_max_radii2D,
+                           float* d_xyz_gradient_accum, float* d_denom, void* stream);
+
+/* scene/gaussian_model.py:densify_and_prune (:393-405) as plan + emit.  Fields are indexed xyz 0, f_dc 1, f_rest 2, opacity 3,
+ * scaling 4, rotation 5; a row of them holds 3, 3, n_rest, 1, 3, 4 floats (n_rest = 3 ((sh_degree + 1)^2 - 1), 0 allowed).
+ * A Gaussian with g = accum / denom (NaN -> 0) >= max_grad is cloned if max(exp(scaling)) <= float(percent_dense * extent) and
+ * split in two otherwise.  Every row of the result -- originals, clones, children on their new scaling -- is then pruned if
+ * sigmoid(opacity) < min_opacity or, with has_max_screen_size, max(exp(scaling)) > float(0.1 * extent).  (The reference's third
+ * term, max_radii2D > max_screen_size, reads an array that densification_postfix has just zeroed: it never fires and is not
+ * evaluated.)  Output rows, each group in source order: surviving originals that were not split, surviving clones, surviving first
+ * children, surviving second children.  d_exp_avg / d_exp_avg_sq entries may be NULL (no optimiser state yet: zeros). */
+typedef struct pixie_gs_densify_desc {
+    int64_t n;
+    int32_t n_rest, has_max_screen_size;
+    double max_grad, min_opacity, extent, percent_dense;
+    const float* d_xyz_gradient_accum;     /* [n] */
+    const float* d_denom;                  /* [n] */
+    const float* d_param[6];
+    const float* d_exp_avg[6];
+    const float* d_exp_avg_sq[6];
+    void* d_workspace;                     /* 16-byte aligned, pixie_gs_densify_workspace_bytes(n) bytes, kept from plan to emit */
+    int64_t workspace_bytes;
+} pixie_gs_densify_desc;
+/* n_out rows of room in every output; d_noise: standard-normal [2 n_split][3], row copy * n_split + (rank among the split). */
+typedef struct pixie_gs_densify_outs {
+    int64_t n_out, n_split;                /* as pixie_gs_densify_plan reported them */
+    const float* d_noise;
+    float* d_param[6];
+    float* d_exp_avg[6];
+    float* d_exp_avg_sq[6];
+    int32_t* d_source_index;               /* [n_out]: the input row each output row came from */
+    float* d_xyz_gradient_accum;           /* [n_out], zero-filled, as d_denom and d_max_radii2D */
+    float* d_denom;
+    float* d_max_radii2D;
+} pixie_gs_densify_outs;
+enum {
+    PIXIE_GS_DENSIFY_BAD_MAX_GRAD = 2,     /* max_grad <= 0 (or NaN): the reference would split its own clones */
+    PIXIE_GS_DENSIFY_TOO_MANY_ROWS = 3,    /* n > 2^31 - 2 */
+    PIXIE_GS_DENSIFY_EMPTY = 4             /* n == 0 */
+};
+int64_t pixie_gs_densify_workspace_bytes(int64_t n);
+/* Classifies, scans and synchronises `stream` ONCE.  counts_out = (surviving originals, clones kept, split children kept, rows the
+ * final prune removed); their first three sum to the output's row count.  n_split_out = Gaussians split (kept or not): the caller
+ * draws 2 n_split rows of noise and allocates the outputs between this call and pixie_gs_densify_emit. */
+int pixie_gs_densify_plan(const pixie_gs_densify_desc* desc, int64_t counts_out[4], int64_t n_split_out[1], void* stream);
+/* One launch, asynchronous.  Survivors keep their moments, new rows get zeros; clones are bit copies; children copy rotation, f_dc,
+ * f_rest and opacity and get scaling = log(exp(scaling) / 1.6), xyz = R(q / |q|) (exp(scaling) * z) + xyz.  outs->n_out and
+ * outs->n_split bound every write and every noise read: a wrong value loses rows, it cannot write outside the outputs. */
+int pixie_gs_densify_emit(const pixie_gs_densify_desc* desc, const pixie_gs_densify_outs* outs, void* stream);
+
 /* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)

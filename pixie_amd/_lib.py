@@ -138,6 +138,39 @@ class IngestDesc(C.Structure):
                 ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class GsAdamGroup(C.Structure):
+    """struct pixie_gs_adam_group"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("count", C.c_int64), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
+
+
+class GsAdamDesc(C.Structure):
+    """struct pixie_gs_adam_desc"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("n_groups", C.c_int32), ("pad_", C.c_int32),
+                ("group", GsAdamGroup * 8)]
+
+
+class GsDensifyDesc(C.Structure):
+    """struct pixie_gs_densify_desc"""
+    _fields_ = [("n", C.c_int64), ("n_rest", C.c_int32), ("has_max_screen_size", C.c_int32),
+                ("max_grad", C.c_double), ("min_opacity", C.c_double), ("extent", C.c_double), ("percent_dense", C.c_double),
+                ("d_xyz_gradient_accum", C.c_void_p), ("d_denom", C.c_void_p),
+                ("d_param", C.c_void_p * 6), ("d_exp_avg", C.c_void_p * 6), ("d_exp_avg_sq", C.c_void_p * 6),
+                ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class GsDensifyOuts(C.Structure):
+    """struct pixie_gs_densify_outs"""
+    _fields_ = [("n_out", C.c_int64), ("n_split", C.c_int64), ("d_noise", C.c_void_p),
+                ("d_param", C.c_void_p * 6), ("d_exp_avg", C.c_void_p * 6), ("d_exp_avg_sq", C.c_void_p * 6),
+                ("d_source_index", C.c_void_p), ("d_xyz_gradient_accum", C.c_void_p), ("d_denom", C.c_void_p),
+                ("d_max_radii2D", C.c_void_p)]
+
+
+# pixie_gs_densify_plan / _emit's return codes besides 0 and 1 (include/pixie_hip.h)
+GS_DENSIFY_BAD_MAX_GRAD, GS_DENSIFY_TOO_MANY_ROWS, GS_DENSIFY_EMPTY = 2, 3, 4
+
+
 # pixie_scene_ingest's return codes besides 0 and 1 (include/pixie_hip.h)
 INGEST_NO_SELECTION, INGEST_ZERO_EXTENT, INGEST_TOO_MANY_ROTATIONS, INGEST_TOO_MANY_ROWS = 2, 3, 4, 5
 
@@ -229,6 +262,11 @@ SIGNATURES = {
     "pixie_photometric_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "pixie_photometric_forward": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _I64, _I, _VP, _VP, _VP]),
     "pixie_photometric_backward": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pixie_gs_adam_step": (_I, [C.POINTER(GsAdamDesc), _VP]),
+    "pixie_gs_densify_stats": (_I, [_VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "pixie_gs_densify_workspace_bytes": (_I64, [_I64]),
+    "pixie_gs_densify_plan": (_I, [C.POINTER(GsDensifyDesc), C.POINTER(_I64), C.POINTER(_I64), _VP]),
+    "pixie_gs_densify_emit": (_I, [C.POINTER(GsDensifyDesc), C.POINTER(GsDensifyOuts), _VP]),
 }
 
 # entry points that exist only in the PIXIE_DIAG build (include/pixie_hip.h, last section)

@@ -790,7 +790,8 @@ int pixie_mpm_phase(pixie_mpm* h, int phase, double dt, void* stream);
 int pixie_mpm_kernel_times(pixie_mpm* h, double* particle_ms, double* grid_ms, int64_t* n_launches);
 
 /* Which kernel instantiation pixie_conv3d_forward picks for this descriptor: ksize*100 + MB*10 + NB of
- * conv3d_f16x3_kernel<ksize,MB,NB> (and its split-K factor in *slices), 9324 = conv3d_f16x3_c64_fullres_kernel (the <3,2,4>
+ * conv3d_f16x3_kernel<ksize,MB,NB> -- with a folded skip convolution: of conv3d_f16x3_skip_kernel<ksize,MB,NB,...>, the same
+ * number -- (and its split-K factor in *slices), 9324 = conv3d_f16x3_c64_fullres_kernel (the <3,2,4>
  * code under its own symbol for the 64 -> 64 full-resolution 3^3 layers), 0 = the exact-fp32 kernel.  For profilers that
  * want to group per-launch timings by kernel name, as rocprofv3 does; no reference counterpart. */
 int pixie_conv_kernel_variant(const pixie_conv_desc* desc, int* slices);

@@ -111,9 +111,10 @@ __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned
 // block nb = 2 px + s holds x parity px of the wave's stored-voxel block s, so the transposing epilogue writes whole output
 // rows.  The tile is staged without the x2 replication with a halo of one voxel on the side the parity reads
 // (x: both sides), i.e. (TX + 2)(TY + 1)(TZ + 1) slots; A.ups is 0 and A.L* are the stored dims on this path.
-template <int KS, int MB, int NB, bool EX = false, bool SP = false>
+template <int KS, int MB, int NB, bool EX = false, bool SP = false, int SK = 0>
 __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     static_assert(!SP || (KS == 3 && NB == 4 && !EX), "sub-pixel path: 3^3, two x parities x two voxel blocks per wave");
+    static_assert(SK == 0 || (!EX && !SP), "folded skip (SK: 1 register-fed, 2 staged through LDS): f16x3, no sub-pixel form");
     extern __shared__ uint4 smem16[];
     constexpr int PAD = (KS == 3) ? 1 : 0;
     constexpr int NW = 4, NT = 64 * NW;     // (an 8-wave, one-workgroup-per-CU tile was measured in round 4: 1.350 vs 1.323 ms, profiles/r4k_conv_eight_wave_tile_rejected.txt)
@@ -536,7 +537,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             __syncthreads();
             mfma_chunk(c_base, smem16);
         }
-        if (!EX && !SP && A.sk_w16) {
+        if constexpr (SK != 0) {
             // ---- the block's 1x1x1 skip convolution, in the same accumulators (so that out = conv(h) + skip(x) leaves this
             // launch; the skip tensor is never written or re-read).  acc holds sum (w s_w)(x s_x); the skip products carry
             // (s_w' s_x') instead, so acc is first multiplied by (s_w' s_x') / (s_w s_x) -- a power of two, exact.
@@ -553,68 +554,152 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
                 for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[mb][nb][r] *= ratio;
-            const int KG2 = A.sk_cin >> 3;
-            const uint4* w2Hi = A.sk_w16 + kW16HeaderU4 + (size_t)kh * A.coutp + cout0 + l31;
-            const uint4* w2Lo = w2Hi + (size_t)KG2 * A.coutp;          // one tap: the lo plane follows the hi plane
-            const int centre = (KS == 3) ? (A.HY + 1) * A.HX + 1 : 0;   // LDS offset of the tile's own voxels inside the halo'd tile
-            const int tvox = A.TX * A.TY * A.TZ;
-            for (int c2 = 0; c2 < A.sk_cin; c2 += 16) {
-                f16x8 ah[MB], al[MB];
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) {
-                    ah[mb] = __builtin_bit_cast(f16x8, w2Hi[(size_t)(c2 >> 3) * A.coutp + mb * 32]);
-                    al[mb] = __builtin_bit_cast(f16x8, w2Lo[(size_t)(c2 >> 3) * A.coutp + mb * 32]);
-                }
-                __syncthreads();   // previous chunk fully consumed
-                uint4* bHi = smem16;
-                uint4* bLo = smem16 + 2 * A.CS;
-                for (int j = tid; j < tvox; j += NT) {   // raw values, interior voxels only (one tap: no halo)
-                    const int x = j & (A.TX - 1), y = (j >> A.lTX) & (A.TY - 1), z = j >> (A.lTX + A.lTY);
-                    const bool okv = (ox0 + x < A.OW) && (oy0 + y < A.OH) && (oz0 + z < A.OD);
-                    const size_t sidx = okv ? ((size_t)(oz0 + z) * A.IH + (oy0 + y)) * A.IW + ox0 + x : 0;
-                    float val[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int cg = c2 + q;
-                        const float* src = (cg < A.sk_c0) ? (A.sk_in0 + (size_t)cg * ISP) : (A.sk_in1 + (size_t)(cg - A.sk_c0) * ISP);
-                        val[q] = src[sidx];
-                    }
-                    f16x8 vh[2], vl[2];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const float sc = okv ? val[q] * sx2 : 0.0f;
-                        const _Float16 hq = (_Float16)sc;
-                        vh[q >> 3][q & 7] = hq;
-                        vl[q >> 3][q & 7] = (_Float16)(sc - (float)hq);
-                    }
-                    const int slot = (z * A.HY + y) * A.HX + x + centre;
-                    bHi[slot] = __builtin_bit_cast(uint4, vh[0]);
-                    bHi[A.CS + slot] = __builtin_bit_cast(uint4, vh[1]);
-                    bLo[slot] = __builtin_bit_cast(uint4, vl[0]);
-                    bLo[A.CS + slot] = __builtin_bit_cast(uint4, vl[1]);
-                }
-                __syncthreads();
-                f16x8 bh[NB], bl[NB];
+            // One tap, so no LDS tile is needed: the B fragment of lane (kh, l31) in block nb is 8 channels of that lane's OWN
+            // voxel, and a wave holds every c_out block of its own voxels -- a staged value is written once and read once, by the
+            // lane that can load it itself.  The lane loads the 8 raw values of channels c2 + 8 kh .. + 7 per block straight from
+            // sk_in0 | sk_in1 and splits them with the arithmetic of the staged form, so the products and their order are the
+            // same.  No barrier, no LDS access: per chunk the 8 NB + 2 MB loads go out back to back, ONE exposed round trip
+            // (staged: three, and two barriers), which the co-resident workgroup's tap loop covers.
+            // Not pipelined across chunks: the forms with the next chunk's loads in flight during this chunk's MFMAs (a second
+            // raw set; one raw set refilled behind the conversion; one or two A sets) all spill on <3,2,4> (246 - 1116 VGPRs) and
+            // cost <1,1,2> and <1,2,2> a wave of occupancy; this one keeps every instantiation at the registers of its twin
+            // without a skip.
+            // Addresses: a raw buffer over the chunk's first channel, the channel as the scalar offset, the lane's voxel (+ 8
+            // channels for kh = 1) as the 32-bit vector offset; the launcher checks that 16 channels span less than 4 GiB.  With
+            // 64-bit lane pointers the compiler keeps an address pair per load (<3,2,4>: 414 spilled VGPRs), and it regroups
+            // global loads from scalar base + lane offset into that form.
+            auto sk_chunks = [&]() {
+                // The lane's geometry is derived again, from copies the optimiser cannot see through: otherwise the offsets are
+                // computed at the top of the kernel, next to voff[] and ovox[], and stay live across the tap loop.
+                int l31s = l31, khs = kh, waves = wave;
+                asm volatile("" : "+v"(l31s), "+v"(khs), "+v"(waves));
+                const unsigned chb = 4u * (unsigned)ISP;     // bytes per channel
+                unsigned off[NB];     // the lane's voxel and k-half in a chunk, in bytes; masked lanes read voxel 0
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
-                    bh[nb] = __builtin_bit_cast(f16x8, bHi[voff[nb] + centre]);
-                    bl[nb] = __builtin_bit_cast(f16x8, bLo[voff[nb] + centre]);
+                    const int j = (waves * NB + nb) * 32 + l31s;
+                    const int x = j & (A.TX - 1), y = (j >> A.lTX) & (A.TY - 1), z = j >> (A.lTX + A.lTY);
+                    off[nb] = (valid[nb] ? 4u * (unsigned)(((oz0 + z) * A.IH + (oy0 + y)) * A.IW + ox0 + x) : 0u) + 8u * (unsigned)khs * chb;
                 }
+                const unsigned wlane = 16u * (unsigned)(khs * A.coutp + l31s);   // byte offset of the lane's A fragment in a k-group pair
+                const char* w2Hi = reinterpret_cast<const char*>(A.sk_w16 + kW16HeaderU4 + cout0);
+                const char* w2Lo = w2Hi + (size_t)(A.sk_cin >> 3) * A.coutp * sizeof(uint4);   // one tap: the lo plane follows the hi plane
+#pragma unroll 1
+                for (int c2 = 0; c2 < A.sk_cin; c2 += 16) {
+                    f16x8 ah[MB], al[MB];
+                    const size_t wrow = (size_t)(c2 >> 3) * A.coutp * sizeof(uint4);
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
+                    for (int mb = 0; mb < MB; ++mb) {
+                        al[mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(w2Lo + wrow + mb * 32 * sizeof(uint4) + wlane));
+                        ah[mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(w2Hi + wrow + mb * 32 * sizeof(uint4) + wlane));
+                    }
+                    // sk_c0 % 16 == 0 here: the chunk's 16 channels lie in one tensor
+                    const float* base = (c2 < A.sk_c0) ? (A.sk_in0 + (size_t)c2 * ISP) : (A.sk_in1 + (size_t)(c2 - A.sk_c0) * ISP);
+                    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, -1, 0x00020000);
+                    float v[NB][8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            v[nb][q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)off[nb], (int)((unsigned)q * chb), 0));
+                    __builtin_amdgcn_sched_barrier(0);   // all loads of the chunk ahead of the first conversion
+                    f16x8 bh[NB], bl[NB];
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
+                        for (int q = 0; q < 8; ++q) {
+                            const float sc = valid[nb] ? v[nb][q] * sx2 : 0.0f;
+                            const _Float16 hq = (_Float16)sc;
+                            bh[nb][q] = hq;
+                            bl[nb][q] = (_Float16)(sc - (float)hq);
+                        }
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
+                    for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);   // the next chunk's loads reuse these registers: they stay below
+                }
+            };
+            if constexpr (SK == 2) {
+                // the parts meet inside a chunk (sk_c0 % 16 == 8; no layer of the networks): staged through LDS, as every folded skip
+                // was before.  The register-fed forms of this case (a lane-valued base, or two exec-masked halves) spill on
+                // <3,2,4>, and so does this loop beside the one above in one kernel: hence instantiations of its own.
+                const int KG2 = A.sk_cin >> 3;
+                const uint4* w2Hi = A.sk_w16 + kW16HeaderU4 + (size_t)kh * A.coutp + cout0 + l31;
+                const uint4* w2Lo = w2Hi + (size_t)KG2 * A.coutp;          // one tap: the lo plane follows the hi plane
+                const int centre = (KS == 3) ? (A.HY + 1) * A.HX + 1 : 0;   // LDS offset of the tile's own voxels inside the halo'd tile
+                const int tvox = A.TX * A.TY * A.TZ;
+                for (int c2 = 0; c2 < A.sk_cin; c2 += 16) {
+                    f16x8 ah[MB], al[MB];
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb) {
+                        ah[mb] = __builtin_bit_cast(f16x8, w2Hi[(size_t)(c2 >> 3) * A.coutp + mb * 32]);
+                        al[mb] = __builtin_bit_cast(f16x8, w2Lo[(size_t)(c2 >> 3) * A.coutp + mb * 32]);
+                    }
+                    __syncthreads();   // previous chunk fully consumed
+                    uint4* bHi = smem16;
+                    uint4* bLo = smem16 + 2 * A.CS;
+                    for (int j = tid; j < tvox; j += NT) {   // raw values, interior voxels only (one tap: no halo)
+                        const int x = j & (A.TX - 1), y = (j >> A.lTX) & (A.TY - 1), z = j >> (A.lTX + A.lTY);
+                        const bool okv = (ox0 + x < A.OW) && (oy0 + y < A.OH) && (oz0 + z < A.OD);
+                        const size_t sidx = okv ? ((size_t)(oz0 + z) * A.IH + (oy0 + y)) * A.IW + ox0 + x : 0;
+                        float val[16];
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) {
+                            const int cg = c2 + q;
+                            const float* src = (cg < A.sk_c0) ? (A.sk_in0 + (size_t)cg * ISP) : (A.sk_in1 + (size_t)(cg - A.sk_c0) * ISP);
+                            val[q] = src[sidx];
+                        }
+                        f16x8 vh[2], vl[2];
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) {
+                            const float sc = okv ? val[q] * sx2 : 0.0f;
+                            const _Float16 hq = (_Float16)sc;
+                            vh[q >> 3][q & 7] = hq;
+                            vl[q >> 3][q & 7] = (_Float16)(sc - (float)hq);
+                        }
+                        const int slot = (z * A.HY + y) * A.HX + x + centre;
+                        bHi[slot] = __builtin_bit_cast(uint4, vh[0]);
+                        bHi[A.CS + slot] = __builtin_bit_cast(uint4, vh[1]);
+                        bLo[slot] = __builtin_bit_cast(uint4, vl[0]);
+                        bLo[A.CS + slot] = __builtin_bit_cast(uint4, vl[1]);
+                    }
+                    __syncthreads();
+                    f16x8 bh[NB], bl[NB];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        bh[nb] = __builtin_bit_cast(f16x8, bHi[voff[nb] + centre]);
+                        bl[nb] = __builtin_bit_cast(f16x8, bLo[voff[nb] + centre]);
+                    }
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                }
+            } else {
+                sk_chunks();
             }
         }
     }
@@ -624,7 +709,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     // registers: per output channel the sum and sum of squares over this workgroup's voxels (lane -> 32-lane DPP
     // reduction -> 4 waves through LDS) go to stats[tile][c_out_padded][2] with plain stores, and the tile's |x|max
     // to *out_amax; pixie_stats_finalize adds the tiles up in fp64.  That replaces one full read of the tensor.
-    const float inv = EX ? 1.0f : (A.sk_w16 ? inv2 : __uint_as_float(A.w16[0].x) * pow2i(-ex));
+    const float inv = EX ? 1.0f : (SK != 0 ? inv2 : __uint_as_float(A.w16[0].x) * pow2i(-ex));
     if (A.partial) {   // split-K slice: raw partial sums; bias, residual and statistics belong to splitk_reduce_kernel
         float* dst = A.partial + (size_t)blockIdx.z * A.cout * OSP;
 #pragma unroll
@@ -814,6 +899,15 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
 template <int KS, int MB, int NB>
 __global__ __launch_bounds__(256, 2) void conv3d_f16x3_kernel(Conv16Args A) {
     conv3d_f16x3_body<KS, MB, NB>(A);
+}
+// The same launch with a folded 1x1x1 skip convolution (SK): instantiations of their own, so that the skip loop's registers are
+// not charged to the kernels that never run it (the sub-pixel path got the same treatment).  conv_plan() can answer
+// skip_foldable with every <KS, MB, NB> of the variant table (without a workspace a small output shrinks NB, then MB), so the
+// table is instantiated whole.
+// STAGED: the skip's parts meet inside a 16-channel chunk (skip_c0 % 16 == 8), see the body.
+template <int KS, int MB, int NB, bool STAGED>
+__global__ __launch_bounds__(256, 2) void conv3d_f16x3_skip_kernel(Conv16Args A) {
+    conv3d_f16x3_body<KS, MB, NB, false, false, STAGED ? 2 : 1>(A);
 }
 // conv_precision = "f32": the exact-fp32 variant of the same body (v_mfma_f32_32x32x2_f32)
 template <int KS, int MB, int NB>
@@ -1235,11 +1329,15 @@ ConvPlan conv_plan(const ConvShape& s) {
 
 // the kernel of a tiled plan: one table for the f16x3 and the exact instantiations
 using ConvKernel = void (*)(Conv16Args);
-static ConvKernel conv16_kernel(const ConvPlan& p) {
+// skip: the descriptor carries a folded skip convolution (f16x3 path, plan.skip_foldable) whose first part has skip_c0 channels
+static ConvKernel conv16_kernel(const ConvPlan& p, bool skip = false, int skip_c0 = 0) {
     if (p.path == CONV_F16X3_SUBPIXEL) return p.MB == 2 ? conv3d_f16x3_subpixel_kernel<2> : conv3d_f16x3_subpixel_kernel<1>;
     if (p.fullres) return conv3d_f16x3_c64_fullres_kernel;
-#define PX_CONV16_PICK(KS_, MB_, NB_) \
-    if (p.KS == KS_ && p.MB == MB_ && p.NB == NB_) return p.path == CONV_EXACT_TILED ? conv3d_exact_kernel<KS_, MB_, NB_> : conv3d_f16x3_kernel<KS_, MB_, NB_>;
+#define PX_CONV16_PICK(KS_, MB_, NB_)                                                                \
+    if (p.KS == KS_ && p.MB == MB_ && p.NB == NB_)                                                   \
+        return p.path == CONV_EXACT_TILED ? conv3d_exact_kernel<KS_, MB_, NB_>                       \
+                                          : (!skip ? conv3d_f16x3_kernel<KS_, MB_, NB_>                                \
+                                                   : ((skip_c0 & 8) ? conv3d_f16x3_skip_kernel<KS_, MB_, NB_, true> : conv3d_f16x3_skip_kernel<KS_, MB_, NB_, false>));
     PX_CONV_VARIANTS(PX_CONV16_PICK)
 #undef PX_CONV16_PICK
     return nullptr;
@@ -1284,6 +1382,8 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
     if (d->d_skip_w16) {
         PX_REQUIRE(p.skip_foldable, "f16x3 conv: this launch cannot fold a skip convolution (pixie_conv_skip_foldable)");
         PX_REQUIRE(d->d_skip_in0 && d->d_skip_amax0 && (d->skip_c1 == 0 || (d->d_skip_in1 && d->d_skip_amax1)), "f16x3 conv: folded skip needs its inputs and their amax slots");
+        // the register-fed skip loop addresses a chunk's 16 channels with a 32-bit byte offset
+        PX_REQUIRE((int64_t)d->in_d * d->in_h * d->in_w * 16 * (int64_t)sizeof(float) < (int64_t)1 << 32, "f16x3 conv: folded skip: 16 channels of the skip input must span less than 4 GiB");
         a.sk_in0 = d->d_skip_in0; a.sk_in1 = d->d_skip_in1; a.sk_c0 = d->skip_c0; a.sk_cin = d->skip_c0 + d->skip_c1;
         a.sk_w16 = reinterpret_cast<const uint4*>(d->d_skip_w16); a.sk_bias = d->d_skip_bias;
         a.sk_amax0 = d->d_skip_amax0; a.sk_amax1 = d->skip_c1 > 0 ? d->d_skip_amax1 : nullptr;
@@ -1294,7 +1394,7 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
     }
     PX_REQUIRE(p.refusal != CONV_BAD_LDS, "f16x3 conv: tile needs %zu B of LDS", p.lds_bytes);
     PX_REQUIRE(p.f16x3(), "f16x3 conv: bad sizes");
-    if (int rc = launch(conv16_kernel(p), p, a, st)) return rc;
+    if (int rc = launch(conv16_kernel(p, a.sk_w16 != nullptr, a.sk_c0), p, a, st)) return rc;
     if (p.slices == 1) return 0;
     const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
     if (d->d_out_stats) {

@@ -13,7 +13,8 @@
 
 namespace pixie {
 
-// The kernel instantiations <KS, MB, NB> of conv3d_f16x3_kernel, conv3d_exact_kernel and (with CK = 4 / 16 channels per LDS
+// The kernel instantiations <KS, MB, NB> of conv3d_f16x3_kernel, conv3d_f16x3_skip_kernel (the same launch with a folded 1x1x1 skip:
+// conv_plan() can answer skip_foldable with every one of them), conv3d_exact_kernel and (with CK = 4 / 16 channels per LDS
 // stage for KS = 3 / 1) the first-generation conv3d_mfma_kernel: MB blocks of 32 output channels x 4 waves x NB blocks of 32 voxels.
 #define PX_CONV_VARIANTS(X) \
     X(3, 2, 4) X(3, 2, 2) X(3, 2, 1) X(3, 1, 4) X(3, 1, 2) X(3, 1, 1) X(1, 2, 4) X(1, 2, 2) X(1, 2, 1) X(1, 1, 4) X(1, 1, 2) X(1, 1, 1)

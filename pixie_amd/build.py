@@ -6,6 +6,7 @@ GPU; the resulting .so is git-ignored but travels with the working tree.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -54,15 +55,26 @@ def _newer(target: str, deps) -> bool:
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def _uses_diag(path: str) -> bool:
+def _uses_diag(path: str, seen=None) -> bool:
+    """Whether the source, or a csrc/ file it includes with quotes (followed recursively), mentions PIXIE_DIAG."""
+    seen = set() if seen is None else seen
+    path = os.path.normpath(path)
+    if path in seen or not os.path.exists(path):
+        return False
+    seen.add(path)
     with open(path) as f:
-        return "PIXIE_DIAG" in f.read()
+        text = f.read()
+    if "PIXIE_DIAG" in text:
+        return True
+    here = os.path.dirname(path)
+    return any(_uses_diag(os.path.join(here, inc), seen) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M)
+               if os.path.normpath(os.path.join(here, inc)).startswith(CSRC + os.sep))
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compiles csrc/*.hip into libpixie_hip.so (the product) and libpixie_hip_diag.so (the same sources with -DPIXIE_DIAG:
     + pixie_mpm_phase / pixie_mpm_kernel_times / pixie_conv_kernel_variant and the kernel trace buffer, for tests and
-    profilers).  Only the sources that mention PIXIE_DIAG are compiled twice.  `force` (or PIXIE_FORCE_BUILD=1 in the
+    profilers).  Only the sources that mention PIXIE_DIAG, themselves or in a csrc/ header they include, are compiled twice.  `force` (or PIXIE_FORCE_BUILD=1 in the
     environment) recompiles everything and prints hipcc's wall time per file, so that a cold build is observable."""
     force = force or os.environ.get("PIXIE_FORCE_BUILD", "") not in ("", "0")
     os.makedirs(OBJ, exist_ok=True)

@@ -42,1547 +42,20 @@
 #include "mpm_math.h"
 #include "splat_math.h"
 
+// One translation unit (the kernels are compiled where they are launched, and this file's name carries its compile flag in build.py),
+// in files by concern.  This one: the solo handle, its launch sequencing and the C API.
+#include "mpm_types.h"               // shared types
+#include "mpm_plan.h"                // the host's decisions as pure functions (tests/test_mpm_plan.py)
+// device code, in the definition order of the code object
+#include "mpm_particle_kernels.h"
+#include "mpm_rebin_kernels.h"
+#include "mpm_grid_kernels.h"
+#include "mpm_batch_kernels.h"
+#include "mpm_dense_grid_kernels.h"
+#include "mpm_setup_kernels.h"
+#include "mpm_export_kernels.h"
+
 namespace pixie {
-
-constexpr int kBS = 4;                    // cells per block edge (particles are binned by the block of their stencil base)
-constexpr int kTS = 8;                    // tile nodes per edge: kBS + 2 (stencil reach) + 2 (one-cell drift margin each side)
-constexpr int kTN = kTS * kTS * kTS;      // 512 nodes
-static_assert(kTN == 512 && kTS == 8, "gather_node recovers the work item from a tile offset with >> 9 and packs tile coordinates in 3 bits");
-constexpr int kWG = 256;                  // particles per work item / threads per workgroup (upper value)
-
-// rows of the particle word array
-enum Row {
-    R_X = 0, R_V = 3, R_F = 6, R_FT = 15, R_C = 24, R_VOL = 33, R_MASS, R_DENSITY, R_E, R_NU, R_MU, R_LAM, R_BULK, R_YS,
-    R_MATERIAL, R_SELECTION, R_PERM, R_XLO, R_XREF = R_XLO + 3, R_COUNT = R_XREF + 3
-    // R_XLO: the low-order part of the position (set_scalar "compensated_x": x_true = x + xlo, |xlo| <= ulp(x)/2; zero otherwise);
-    // R_XREF: position at the last re-binning (must stay the last rows: bin_permute_kernel fills them from x)
-};
-static_assert(R_COUNT == 51, "row table");
-
-struct MpmPtrs {
-    int n, ng, nbk;   // particles, grid nodes per axis, blocks per axis
-    float dx, inv_dx;
-    float *x, *v, *F, *Ft, *C;  // SoA: [3][n], [3][n], [9][n], [9][n], [9][n]
-    float *vol, *mass, *density, *E, *nu, *mu, *lam, *bulk, *ys;
-    int *material, *selection, *perm;
-    float* xref;                 // [3][n] positions at the last re-binning (drift measurement)
-    float* xlo;                  // [3][n] what the float32 position leaves behind (compensated_x), see particle_phase1
-    float4 *gin, *gout;
-    const int4* items;           // work list: (block id, first slot, count, 0)
-    float4* part;                // [n_items][kTN]: (m*v.xyz, m) of each work item's tile, written by its P2G
-    unsigned long long* tile_mask;  // [n_items][8]: bit t of a tile = "node t (tile coordinates, z fastest) is not all zero"
-    unsigned zero_off;           // index (float4 units) of an all-zero tile behind the work items' tiles: what a gather reads where there is nothing to read
-    int sparse_tiles;            // 1: P2G stores only the non-zero nodes of a tile and the grid kernel reads only those (masks);
-                                 // 0: whole tiles both ways (scenes too small to be bandwidth-bound: one dependent load fewer)
-    const int2* blk_items;       // per block: (first work item, number of work items)
-    int* blk_flags;              // per block: bit 0 = active (particles nearby), bit 1 = slow-path particles wrote into gin here
-    const int* active_list;      // the active blocks
-    const int2* nbr_table;       // per active block (same order): [0] = (block id, 0), [1..27] = blk_items of its 27 neighbours
-    const unsigned* staged_lut;  // [256]: staged_index of tile nodes t (low half) and t + 256 (high half)
-    unsigned long long* oob;     // [0] particles skipped because their stencil left the grid, [1] slow-path particles,
-                                 // [2] slow-path particles dropped because they had left every active block
-};
-
-struct StepParams {
-    float dt, time;
-    float g[3];
-    float damping;
-    int do_damping;
-    float rpic;
-    int xcd_order;  // set_scalar "xcd_order": work items dealt to the XCDs in contiguous runs (see mpm_block_kernel)
-    int comp_x;     // set_scalar "compensated_x": carry the rounding error of x += dt v in xlo (see particle_phase1)
-    int trace;      // timing studies: bit 0 = workgroups stamp s_memrealtime around their phases into g_mpm_trace;
-                    // bits 8.. = ablations for bottleneck hunting (RESULTS ARE WRONG with any of them set):
-                    // 0x100 skip the LDS scatter atomics, 0x200 skip the workgroup scale reduction (fixed scale),
-                    // 0x400 skip the tile staging loads, 0x800 skip the tile publish stores
-    MaterialScalars ms;
-};
-
-struct BCDev {
-    int type, surface_type, reset, pad;
-    float point[3], size[3], velocity[3], normal[3];
-    float start, end, friction;
-};
-constexpr int kMaxBCPerLaunch = 16;
-struct BCSet {
-    int n;
-    BCDev bc[kMaxBCPerLaunch];
-};
-
-struct PModDev {
-    int type;
-    float point[3], force[3], velocity[3], normal[3], h1[3], h2[3];
-    float rot_scale, trans_scale, start, end;
-    const int* mask;   // [n] in the CALLER's particle order (index through perm)
-};
-constexpr int kMaxPModFused = 8;
-struct PModSet {
-    int n;
-    PModDev pm[kMaxPModFused];
-};
-
-// Position of tile node (lx,ly,lz) inside a STAGED tile (part[item][512]).  A tile starts one node before its block, so
-// along each axis its 8 nodes fall into three grid blocks: {0}, {1..4}, {5..7}.  The staged tile is stored sub-box by
-// sub-box (27 boxes of 1|4|3 nodes per axis, each contiguous) so that the grid kernel, whose wave owns one 4x4x4 grid
-// block, reads ONE contiguous run per covering tile instead of 16 64-byte rows scattered over 128-byte lines
-// (measured: 3x over-fetch with the plain row-major tile).
-__host__ __device__ __forceinline__ int staged_index(int lx, int ly, int lz) {
-    const int sx = (lx == 0) ? 0 : (lx <= 4 ? 1 : 2), sy = (ly == 0) ? 0 : (ly <= 4 ? 1 : 2), sz = (lz == 0) ? 0 : (lz <= 4 ? 1 : 2);
-    const int ox = (sx == 0) ? 0 : (sx == 1 ? 1 : 5), oy = (sy == 0) ? 0 : (sy == 1 ? 1 : 5), oz = (sz == 0) ? 0 : (sz == 1 ? 1 : 5);
-    const int ny = (sy == 0) ? 1 : (sy == 1 ? 4 : 3), nz = (sz == 0) ? 1 : (sz == 1 ? 4 : 3);
-    // nodes in the sub-boxes that precede (sx,sy,sz): full x-slabs, then full y-rows of this slab, then z-boxes of this row
-    const int nx = (sx == 0) ? 1 : (sx == 1 ? 4 : 3);
-    const int before = ox * 64 + nx * (oy * 8 + ny * oz);
-    return before + ((lx - ox) * ny + (ly - oy)) * nz + (lz - oz);
-}
-
-// ------------------------------------------------------------------ particle modifiers
-// apply_force (mpm_solver_warp.py:1015-1027), modify_particle_v_before_p2g (:1061-1073, :1137-1179)
-__device__ __forceinline__ void apply_pmod(const PModDev& m, int caller_idx, float time, float dt, float mass,
-                                           const float x[3], float v[3]) {
-    if (!(time >= m.start && time < m.end)) return;
-    if (m.mask[caller_idx] != 1) return;
-    if (m.type == PIXIE_PM_IMPULSE) {
-        for (int d = 0; d < 3; ++d) v[d] = v[d] + (m.force[d] / mass) * dt;
-    } else if (m.type == PIXIE_PM_TRANSLATION) {
-        for (int d = 0; d < 3; ++d) v[d] = m.velocity[d];
-    } else {
-        const float o[3] = {x[0] - m.point[0], x[1] - m.point[1], x[2] - m.point[2]};
-        const float dn = o[0] * m.normal[0] + o[1] * m.normal[1] + o[2] * m.normal[2];
-        const float hx = o[0] - dn * m.normal[0], hy = o[1] - dn * m.normal[1], hz = o[2] - dn * m.normal[2];
-        const float hd = sqrtf(hx * hx + hy * hy + hz * hz);
-        const float cosine = (o[0] * m.h1[0] + o[1] * m.h1[1] + o[2] * m.h1[2]) / hd;
-        float theta = acosf(cosine);
-        if (!((o[0] * m.h2[0] + o[1] * m.h2[1] + o[2] * m.h2[2]) > 0.0f)) theta = -theta;
-        const float a1 = -hd * sinf(theta) * m.rot_scale;
-        const float a2 = hd * cosf(theta) * m.rot_scale;
-        for (int d = 0; d < 3; ++d) v[d] = a1 * m.h1[d] + a2 * m.h2[d] + m.trans_scale * m.normal[d];
-    }
-}
-
-__device__ __forceinline__ bool stencil_inside(const Stencil& st, int ng) {
-    bool ok = true;
-    for (int d = 0; d < 3; ++d) ok = ok && (st.base[d] >= 0) && (st.base[d] + 2 < ng);
-    return ok;
-}
-
-// ------------------------------------------------------------------ separable transfer cores
-// The 27-node sums of g2p (mpm_utils.py:436-455) and p2g_apic_with_stress (:360-393) are tensor products of
-// 1-D quadratic B-spline weights, so they are evaluated axis by axis (z innermost): 9 FMAs per node
-// instead of ~28.  This only re-associates the reference's fp32 sums.
-struct Weights1D {
-    float w[3], dw[3], wd[3];  // weight, derivative (cell units), weight * (offset - fx)
-};
-__device__ __forceinline__ void weights_1d(const Stencil& st, int d, Weights1D& o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        o.w[i] = st.w[d][i];
-        o.dw[i] = st.dw[d][i];
-        o.wd[i] = st.w[d][i] * ((float)i - st.fx[d]);
-    }
-}
-
-// v = sum w g;  B_ab = sum w g_a dpos_b (cell units);  G_ab = sum g_a dweight_b (cell units)
-// Two contractions of every node value g_a(i,j,k) carry all 21 sums (6 FMAs per node instead of 9; 288 VALU instructions per
-// particle instead of 441 -- round 4, the kernel is VALU-issue bound):
-//   s_a(i,j) = sum_k wz_k g_a       -> the x- and y-derivative columns:  ss_a(i) = sum_j wy_j s_a,  t_a(j) = sum_i wx_i s_a
-//   h_a(k)   = sum_ij wx_i wy_j g_a -> v and the z-derivative column
-//   v_a = sum_k wz_k h_a(k);   G_a0 = sum_i dwx_i ss_a(i),  G_a1 = sum_j dwy_j t_a(j),  G_a2 = sum_k dwz_k h_a(k);   B likewise with wd.
-// SCHED: keep the loads of one x-slab from being hoisted over the previous slab's arithmetic (the 5-waves-per-SIMD register
-// budget needs it; the wide variant for small scenes, F_WIDE, lets the compiler overlap everything).
-template <bool SCHED, class Fetch>
-__device__ __forceinline__ void g2p_gather(const Stencil& st, Fetch fetch, float nv[3], Mat3& B, Mat3& G) {
-    Weights1D wx, wy, wz;
-    weights_1d(st, 0, wx); weights_1d(st, 1, wy); weights_1d(st, 2, wz);
-    float h[3][3], t[3][3], g0[3], b0[3];   // h[k][a], t[j][a]
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        g0[a] = 0.0f; b0[a] = 0.0f;
-#pragma unroll
-        for (int o = 0; o < 3; ++o) { h[o][a] = 0.0f; t[o][a] = 0.0f; }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float ss[3] = {0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float wij = wx.w[i] * wy.w[j];
-            float s[3] = {0, 0, 0};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float g[3];
-                fetch(i, j, k, g);
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    s[a] = fmaf(wz.w[k], g[a], s[a]);
-                    h[k][a] = fmaf(wij, g[a], h[k][a]);
-                }
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                ss[a] = fmaf(wy.w[j], s[a], ss[a]);
-                t[j][a] = fmaf(wx.w[i], s[a], t[j][a]);
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            g0[a] = fmaf(wx.dw[i], ss[a], g0[a]);
-            b0[a] = fmaf(wx.wd[i], ss[a], b0[a]);
-        }
-        if (SCHED) __builtin_amdgcn_sched_barrier(0);  // keep the 27 loads of the next x-slab from being hoisted over this one
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        nv[a] = fmaf(wz.w[2], h[2][a], fmaf(wz.w[1], h[1][a], wz.w[0] * h[0][a]));
-        G.m[3 * a + 0] = g0[a];
-        B.m[3 * a + 0] = b0[a];
-        G.m[3 * a + 1] = fmaf(wy.dw[2], t[2][a], fmaf(wy.dw[1], t[1][a], wy.dw[0] * t[0][a]));
-        B.m[3 * a + 1] = fmaf(wy.wd[2], t[2][a], fmaf(wy.wd[1], t[1][a], wy.wd[0] * t[0][a]));
-        G.m[3 * a + 2] = fmaf(wz.dw[2], h[2][a], fmaf(wz.dw[1], h[1][a], wz.dw[0] * h[0][a]));
-        B.m[3 * a + 2] = fmaf(wz.wd[2], h[2][a], fmaf(wz.wd[1], h[1][a], wz.wd[0] * h[0][a]));
-    }
-}
-
-// momentum_a(i,j,k) = w (mv_a + A_a . dpos) + T_a . gradw,  mass(i,j,k) = w m   with A = m C' dx (dpos in cell
-// units) and T = -dt vol inv_dx tau (gradw in cell units).  Grouped by axis (wd = w * offset, dw = dw/dx in cell units):
-//   momentum_a = wz_k [ wy_j E_a(i) + wx_i U_a(j) ] + wx_i wy_j S_a(k)
-//   E_a(i) = wx_i mv_a + A_a0 wdx_i + T_a0 dwx_i,   U_a(j) = A_a1 wdy_j + T_a1 dwy_j,   S_a(k) = A_a2 wdz_k + T_a2 dwz_k
-// U and S do not depend on the other axes and are formed once per particle: 7 VALU instructions per node, 8 per (i, j)
-// pair, 9 per x-slab, 36 once -- 324 per particle (round 3: 486; the block kernel is VALU-issue bound).
-template <bool SCHED, class Emit>
-__device__ __forceinline__ void p2g_scatter(const Stencil& st, const float mv[3], const Mat3& A, const Mat3& T, float mass, Emit emit) {
-    Weights1D wx, wy, wz;
-    weights_1d(st, 0, wx); weights_1d(st, 1, wy); weights_1d(st, 2, wz);
-    float U[3][3], S[3][3];   // [component][offset]
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int o = 0; o < 3; ++o) {
-            U[a][o] = fmaf(A.m[3 * a + 1], wy.wd[o], T.m[3 * a + 1] * wy.dw[o]);
-            S[a][o] = fmaf(A.m[3 * a + 2], wz.wd[o], T.m[3 * a + 2] * wz.dw[o]);
-        }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float E[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) E[a] = fmaf(A.m[3 * a + 0], wx.wd[i], fmaf(T.m[3 * a + 0], wx.dw[i], wx.w[i] * mv[a]));
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float wij = wx.w[i] * wy.w[j];
-            float P[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) P[a] = fmaf(E[a], wy.w[j], wx.w[i] * U[a][j]);
-            const float M = wij * mass;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float mom[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) mom[a] = fmaf(wz.w[k], P[a], wij * S[a][k]);
-                emit(i, j, k, mom, wz.w[k] * M);
-            }
-        }
-        if (SCHED) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// ---- slow path: a particle whose stencil lies outside its workgroup's tile talks to HBM directly.  Rare
-// (stale binning only), so it is kept out of line and rolled to stay out of the fast path's register budget.
-__device__ __noinline__ void g2p_gather_global(const float4* __restrict__ gout, int ng, Stencil st, float* nv9 /* nv[3], B[9], G[9] */) {
-    float nv[3] = {0, 0, 0}, B[9], G[9];
-    for (int q = 0; q < 9; ++q) { B[q] = 0.0f; G[q] = 0.0f; }
-    const size_t r0 = ((size_t)st.base[0] * ng + st.base[1]) * ng + st.base[2];
-#pragma unroll 1
-    for (int t = 0; t < 27; ++t) {
-        const int i = t / 9, j = (t / 3) % 3, k = t % 3;
-        const float4 q = gout[r0 + ((size_t)i * ng + j) * ng + k];
-        const float g[3] = {q.x, q.y, q.z};
-        const float w = st.w[0][i] * st.w[1][j] * st.w[2][k];
-        const float gw[3] = {st.dw[0][i] * st.w[1][j] * st.w[2][k], st.w[0][i] * st.dw[1][j] * st.w[2][k],
-                             st.w[0][i] * st.w[1][j] * st.dw[2][k]};
-        const float dp[3] = {(float)i - st.fx[0], (float)j - st.fx[1], (float)k - st.fx[2]};
-        for (int a = 0; a < 3; ++a) {
-            nv[a] += w * g[a];
-            for (int b = 0; b < 3; ++b) {
-                B[3 * a + b] += w * g[a] * dp[b];
-                G[3 * a + b] += g[a] * gw[b];
-            }
-        }
-    }
-    for (int a = 0; a < 3; ++a) nv9[a] = nv[a];
-    for (int q = 0; q < 9; ++q) { nv9[3 + q] = B[q]; nv9[12 + q] = G[q]; }
-}
-
-__device__ __noinline__ bool p2g_scatter_global(float4* gin, int* blk_flags, int nbk, int ng, Stencil st,
-                                                const float* mvAT /* mv[3], A[9], T[9] */, float mass) {
-    const size_t r0 = ((size_t)st.base[0] * ng + st.base[1]) * ng + st.base[2];
-    // the 3x3x3 stencil touches at most 2 blocks per axis: tell the grid kernel they hold gin contributions.  The grid
-    // kernel only visits ACTIVE blocks (particles within one block at the last re-binning); a particle that has left
-    // all of them drifted >= 3 cells since then although the re-binning cadence is set to keep the drift below half a
-    // cell (rebin()) -- it is dropped and counted, like a particle that leaves the grid.
-    bool reachable = true;
-    for (int c = 0; c < 8; ++c) {
-        const int bx = (st.base[0] + 2 * (c >> 2)) / kBS, by = (st.base[1] + 2 * ((c >> 1) & 1)) / kBS, bz = (st.base[2] + 2 * (c & 1)) / kBS;
-        reachable = reachable && (atomicOr(&blk_flags[(bx * nbk + by) * nbk + bz], 2) & 1);
-    }
-    if (!reachable) return false;
-#pragma unroll 1
-    for (int t = 0; t < 27; ++t) {
-        const int i = t / 9, j = (t / 3) % 3, k = t % 3;
-        const float w = st.w[0][i] * st.w[1][j] * st.w[2][k];
-        const float gw[3] = {st.dw[0][i] * st.w[1][j] * st.w[2][k], st.w[0][i] * st.dw[1][j] * st.w[2][k],
-                             st.w[0][i] * st.w[1][j] * st.dw[2][k]};
-        const float dp[3] = {(float)i - st.fx[0], (float)j - st.fx[1], (float)k - st.fx[2]};
-        float* cell = reinterpret_cast<float*>(gin + r0 + ((size_t)i * ng + j) * ng + k);
-        for (int a = 0; a < 3; ++a) {
-            const float* A = mvAT + 3 + 3 * a;
-            const float* T = mvAT + 12 + 3 * a;
-            const float mom = w * (mvAT[a] + A[0] * dp[0] + A[1] * dp[1] + A[2] * dp[2]) + T[0] * gw[0] + T[1] * gw[1] + T[2] * gw[2];
-            unsafeAtomicAdd(cell + a, mom);
-        }
-        unsafeAtomicAdd(cell + 3, w * mass);
-    }
-    return true;
-}
-
-// ------------------------------------------------------------------ fused block kernel
-// G2P part: g2p (mpm_utils.py:412-463).  P2G part: pre-P2G modifiers, compute_stress_from_F_trial
-// (:467-526) and p2g_apic_with_stress (:338-394).  `sp.time` is the time of the substep whose P2G runs.
-//
-// The scatter accumulates in LDS with 64-bit INTEGER atomics: ds_add_f32 retires ~1 lane per 3 cycles on gfx950
-// (193 cycles per wave-instruction, measured: scripts/microbench/lds_atomics.hip), ds_add_u64 is 11x faster.  Each
-// workgroup therefore (1) computes every particle's scatter inputs, (2) takes the workgroup maximum of a bound on
-// their contributions, (3) scales by the power of two that puts that bound just below 2^42 and adds round-to-nearest
-// integers (|sum of 256| < 2^50; see to_fixed).  The LSB is 2^-42 of the largest contribution in the tile, i.e. the tile
-// sums are exact to ~2e-13 -- tighter than any fp32 summation order -- and since integer adds commute they are bit-reproducible.
-// (A 32-bit variant -- LSB 2^-21 -- was measured first: low-mass free-surface nodes lost up to 10 % of their velocity.)
-struct ScatterIn {
-    float x[3];     // position after the G2P update (where the P2G stencil is taken)
-    float mv[3];    // mass * v
-    Mat3 A;         // mass * C' * dx
-    Mat3 T;         // -dt * vol * inv_dx * tau
-    float mass;
-    bool active;    // contributes to P2G
-};
-
-// what a particle needs from HBM before it can start: issued BEFORE the tile load + barrier so that the two latencies overlap
-struct Preload {
-    float x[3];
-    Mat3 F;          // fused kernel: F of the previous substep (G2P input); P2G-only kernel: unused
-    float mass, vol, mu, lam;
-    int material, selection;
-};
-template <bool DO_G2P, bool DO_P2G>
-__device__ __forceinline__ void preload_particle(const MpmPtrs& S, int p, Preload& L) {
-    const int n = S.n;
-    L.selection = S.selection[p];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) L.x[d] = S.x[d * n + p];
-    if (DO_G2P) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) L.F.m[i] = S.F[i * n + p];
-    }
-    if (DO_P2G) {
-        L.mass = S.mass[p]; L.vol = S.vol[p]; L.mu = S.mu[p]; L.lam = S.lam[p]; L.material = S.material[p];
-    }
-}
-
-// What a caller reads from a particle that has just been frozen outside the grid: zero velocity and APIC matrix, and its last
-// deformation gradient as F_trial.  (The fused kernel keeps v, C and F_trial of the particles that take part in registers, and a
-// re-binning does not move those rows for them -- bin_permute_kernel -- so the rows of a particle that drops out are written here.)
-// (inlined, a rolled loop of plain stores: an out-of-line function taking the kernel's parameter struct by reference copies it to
-// scratch -- 404 -> 740 bytes per lane, beyond the cliff of profiles/r6e_scratch_regression.txt)
-__device__ __forceinline__ void freeze_particle_state(const MpmPtrs& S, int p, const Mat3& F) {
-    const int n = S.n;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) S.v[d * n + p] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { S.C[i * n + p] = 0.0f; S.Ft[i * n + p] = F.m[i]; }
-}
-
-template <bool DO_G2P, bool DO_P2G, bool SCHED>
-__device__ __forceinline__ void particle_phase1(const MpmPtrs& S, const StepParams& sp, const PModSet& pms, int p, int ox, int oy,
-                                                int oz, const float4* tv, const Preload& L, ScatterIn& out) {
-    out.active = false;
-    if (L.selection != 0) return;
-    const int n = S.n;
-    float x[3], v[3];
-    Mat3 C, Ft;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[d] = L.x[d];
-
-    if (DO_G2P) {
-        const Stencil st = make_stencil(x[0], x[1], x[2], S.inv_dx);
-        if (!stencil_inside(st, S.ng)) {
-            atomicAdd(S.oob, 1ull);
-            S.selection[p] = 2;   // left the grid: frozen from now on and counted once (UB in the reference)
-            freeze_particle_state(S, p, L.F);
-            return;
-        }
-        const Mat3& Fold = L.F;
-        float nv[3];
-        Mat3 B, G;
-        const int lx = st.base[0] - ox, ly = st.base[1] - oy, lz = st.base[2] - oz;
-        if ((unsigned)lx <= (unsigned)(kTS - 3) && (unsigned)ly <= (unsigned)(kTS - 3) && (unsigned)lz <= (unsigned)(kTS - 3)) {
-            const int b0 = (lx * kTS + ly) * kTS + lz;
-            g2p_gather<SCHED>(st, [&](int i, int j, int k, float g[3]) {
-                // One ds_read_b128 per node.  The .w lane is dead, but a 16-byte LDS read costs 4 LDS cycles per wave against
-                // 8 for the 12-byte ds_read_b96 the compiler would narrow it to (MI355X_MICROARCH.md, LDS table), and LDS
-                // and VALU time add up in this kernel (80.7 -> 78.4 us per launch at 1 M particles): keep the lane alive.
-                const float4 q = tv[b0 + (i * kTS + j) * kTS + k];
-                asm volatile("" :: "v"(q.w));
-                g[0] = q.x; g[1] = q.y; g[2] = q.z;
-            }, nv, B, G);
-        } else {
-            atomicAdd(S.oob + 1, 1ull);
-            float acc[21];
-            g2p_gather_global(S.gout, S.ng, st, acc);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) nv[a] = acc[a];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) { B.m[q] = acc[3 + q]; G.m[q] = acc[12 + q]; }
-        }
-        Mat3 Amat;
-        const float sdt = sp.dt * S.inv_dx;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Amat.m[i] = ((i % 4 == 0) ? 1.0f : 0.0f) + G.m[i] * sdt;
-        Ft = mat_mul(Amat, Fold);
-        const float sc = 4.0f * S.inv_dx;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) C.m[i] = B.m[i] * sc;
-        // x += dt v in float32 (mpm_utils.py:447) drops whatever of dt v lies below ulp(x)/2 = 6e-8 at x ~ 1: in a quiet scene
-        // (dt v ~ 1e-7) most of the motion, systematically -- the reference's own float32 behaviour, and the default here.
-        // "compensated_x" keeps what was dropped in xlo and feeds it into the next increment (Kahan): x is then the float32
-        // ROUNDING of the accumulated position instead of a sum of rounded increments (3 more words per particle each way).
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            v[d] = nv[d];
-            if (sp.comp_x) {
-                const float y = sp.dt * nv[d] + S.xlo[d * n + p];
-                const float t = x[d] + y;
-                S.xlo[d * n + p] = y - (t - x[d]);
-                x[d] = t;
-            } else {
-                x[d] = x[d] + sp.dt * nv[d];
-            }
-            S.x[d * n + p] = x[d];
-        }
-        if (!DO_P2G) {  // the state a caller can observe: x, v, C, F_trial
-#pragma unroll
-            for (int d = 0; d < 3; ++d) S.v[d * n + p] = v[d];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                S.C[i * n + p] = C.m[i];
-                S.Ft[i * n + p] = Ft.m[i];
-            }
-            return;
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) v[d] = S.v[d * n + p];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            C.m[i] = S.C[i * n + p];
-            Ft.m[i] = S.Ft[i * n + p];
-        }
-    }
-
-    if (DO_P2G) {
-        const float mass = L.mass;
-        if (pms.n > 0) {
-            const float v_before[3] = {v[0], v[1], v[2]};
-            const int ci = S.perm[p];
-            for (int k = 0; k < pms.n; ++k) apply_pmod(pms.pm[k], ci, sp.time, sp.dt, mass, x, v);
-            if (!DO_G2P && (v[0] != v_before[0] || v[1] != v_before[1] || v[2] != v_before[2]))
-                for (int d = 0; d < 3; ++d) S.v[d * n + p] = v[d];
-        }
-        const int material = L.material;
-        float mu = L.mu, lam = L.lam;
-        float ys = (material == 1 || material == 3 || material == 5) ? S.ys[p] : 0.0f;
-        const float bulk = (material == 6) ? S.bulk[p] : 0.0f;
-        const float mu0 = mu, lam0 = lam, ys0 = ys;
-        Mat3 F, tau;
-        return_map_and_stress(material, Ft, mu, lam, bulk, ys, sp.ms, sp.dt, F, tau);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) S.F[i * n + p] = F.m[i];
-        if (ys != ys0) S.ys[p] = ys;
-        if (mu != mu0) S.mu[p] = mu;
-        if (lam != lam0) S.lam[p] = lam;
-
-        // C' = (1-r) C + r/2 (C - C^T);  r < -0.001 => PIC (mpm_utils.py:372-379)
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                float c = (1.0f - sp.rpic) * C.m[3 * a + b] + sp.rpic * 0.5f * (C.m[3 * a + b] - C.m[3 * b + a]);
-                if (sp.rpic < -0.001f) c = 0.0f;
-                out.A.m[3 * a + b] = mass * c * S.dx;  // dpos = (ijk - fx) * dx
-            }
-        const float ks = -sp.dt * L.vol * S.inv_dx;  // dt * (-vol * tau * dweight), dweight = dw*w*w*inv_dx
-#pragma unroll
-        for (int i = 0; i < 9; ++i) out.T.m[i] = ks * tau.m[i];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { out.mv[d] = mass * v[d]; out.x[d] = x[d]; }
-        out.mass = mass;
-        out.active = true;
-    }
-}
-
-// ---- fixed-point accumulation of the scatter ---------------------------------------------------------------------------
-// EXACT mode (set_scalar "scatter_bits" 64): 64-bit fixed point through the double-precision adder: the mantissa field of (x + 1.5 * 2^52) is
-// 2^51 + round(x) for |x| < 2^51, so ds_add_u64 of the raw bit patterns accumulates sum(round(x_i)) modulo 2^51 in the low
-// 51 bits whatever happens above them (the N copies of the exponent and of the 2^51 offset only carry upwards).  With every
-// contribution scaled below 2^42 and at most 256 of them per node the sum stays below 2^50 and is recovered by
-// sign-extending bit 50: two instructions per contribution (v_cvt_f64_f32, v_add_f64), exact integer accumulation,
-// order-independent.
-// PACKED mode (F_PACK32, the default; "scatter_bits" 32): two 32-bit two's-complement integers per ds_add_u64 -- (m*v.x, m*v.y)
-// and (m, m*v.z) -- so a node costs 2 LDS atomics instead of 4 and 6 plain VALU instructions instead of 8 double-rate ones.
-// The contributions are scaled so that the sum of the particles' bounds is below 2^30 (see the scales in the kernel) and
-// rounded to nearest by v_cvt_rpi_i32_f32; the
-// pair word is low + (high << 32) in 64-bit arithmetic, i.e. the high dword carries `high + (low >> 31)`, and the decode
-// undoes exactly that, so the two sums are exact integers and order-independent like the 64-bit ones.  What changes is the
-// quantum: 2^-30 of the SUM of the contribution bounds of the tile's particles instead of 2^-42 of their maximum -- the
-// order of the fp32 atomics of the reference (2^-24 of each partial sum) for nodes that carry mass, but a node whose whole
-// mass is below ~1e-7 of a particle's (stencil corners at a free surface) is quantised visibly: see HISTORY.md 3.5 and
-// tests/test_mpm_hip.py::test_packed_scatter_parity.
-constexpr double kMagicD = 6755399441055744.0;            // 1.5 * 2^52
-
-// power of two s with bound * s in [2^top, 2^(top+1))  (1 when the bound is zero / not finite)
-__device__ __forceinline__ float scale_for(float bound, int top) {
-    const unsigned bits = __float_as_uint(bound);
-    const int eb = (int)((bits >> 23) & 0xffu) - 127;
-    if (!(bound > 0.0f) || eb > 120) return 1.0f;
-    int e = top - eb;
-    e = e > 120 ? 120 : (e < -80 ? -80 : e);
-    return __uint_as_float((unsigned)(e + 127) << 23);
-}
-// 1 / s for s = 2^e, exactly, without a division (|e| <= 120: scale_for)
-__device__ __forceinline__ float pow2_reciprocal(float s) {
-    return __uint_as_float(0x7f000000u - __float_as_uint(s));
-}
-__device__ __forceinline__ unsigned long long to_fixed(float scaled) {
-    return (unsigned long long)__double_as_longlong((double)scaled + kMagicD);
-}
-// low 51 bits, sign-extended, as a float: flipping bit 50 turns the field into (sum + 2^50) >= 0, which is dropped into the
-// mantissa of 2^52 and the two offsets subtracted again -- exact (|sum| < 2^50), and no 64-bit integer conversion
-__device__ __forceinline__ float from_fixed(unsigned long long v, float inv_scale) {
-    const unsigned hi = (((unsigned)(v >> 32) & 0x7ffffu) ^ 0x40000u) | 0x43300000u;
-    const double d = __hiloint2double((int)hi, (int)(unsigned)v) - 5629499534213120.0;   // 2^52 + 2^50
-    return (float)(d * (double)inv_scale);
-}
-__device__ __forceinline__ int round_to_int(float x) {   // floor(x + 0.5): one instruction (CDNA keeps GCN's v_cvt_rpi)
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ int round_to_int_neg(float x) {   // floor(-x + 0.5): the negation rides in the VOP3 source modifier
-    int r;
-    asm("v_cvt_rpi_i32_f32_e64 %0, -%1" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ unsigned long long pack_pair(int low, int high) {
-    return (unsigned long long)(unsigned)low | ((unsigned long long)(unsigned)(high + (low >> 31)) << 32);
-}
-__device__ __forceinline__ void unpack_pair(unsigned long long w, int& low, int& high) {
-    low = (int)(unsigned)w;
-    high = (int)(unsigned)(w >> 32) - (low >> 31);
-}
-
-// Maximum of a non-negative float over the wave, in the DPP network (no LDS round trips: __shfl_xor is ds_bpermute, six
-// dependent ~60-cycle LDS operations per value).  Non-negative floats order like their bit patterns, so the maximum is
-// taken on integers (no NaN canonicalisation instructions; a NaN bound comes out as the maximum, which scale_for maps to 1).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umax(unsigned v) {
-    // lanes the pattern does not feed (masked rows) read their own value: old = v, bound_ctrl off
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-    return max(v, o);
-}
-// Sum over the wave in the same network (fixed tree: reproducible).  Lanes a masked row pattern does not feed add 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __int_as_float(o);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v = dpp_add<0xB1, 0xf>(v);
-    v = dpp_add<0x4E, 0xf>(v);
-    v = dpp_add<0x141, 0xf>(v);
-    v = dpp_add<0x140, 0xf>(v);     // every lane of a row of 16 holds the row sum
-    v = dpp_add<0x142, 0xa>(v);     // rows 1, 3 += rows 0, 2
-    v = dpp_add<0x143, 0xc>(v);     // rows 2, 3 += row 1 (= rows 0 + 1): lane 63 holds the wave sum
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ float wave_max_nonneg(float x) {
-    unsigned v = __float_as_uint(x);
-    v = dpp_umax<0xB1, 0xf>(v);     // quad_perm [1,0,3,2]
-    v = dpp_umax<0x4E, 0xf>(v);     // quad_perm [2,3,0,1]
-    v = dpp_umax<0x141, 0xf>(v);    // row_half_mirror
-    v = dpp_umax<0x140, 0xf>(v);    // row_mirror: every lane of a row of 16 holds the row maximum
-    v = dpp_umax<0x142, 0xa>(v);    // row_bcast:15 into rows 1 and 3
-    v = dpp_umax<0x143, 0xc>(v);    // row_bcast:31 into rows 2 and 3: lane 63 holds the wave maximum
-    return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)v, 63));
-}
-
-// Phase trace (pixie_mpm_set_scalar "trace" 1; read back with pixie::mpm_trace_read, not part of the C ABI): per work item 8
-// 100 MHz timestamps -- start, tile staged, particles updated (G2P + stress), scales known, scatter done, tile published.
-// The trace buffer, the F_TRACE instantiation and every diagnostic entry point exist only in the -DPIXIE_DIAG build
-// (libpixie_hip_diag.so: tests and profilers); the production library carries none of it.
-#ifdef PIXIE_DIAG
-constexpr int kMpmTraceItems = 32768;
-__device__ unsigned long long g_mpm_trace[kMpmTraceItems * 8];
-#define PX_MPM_STAMP(i) do { if ((FL & F_TRACE) && (sp.trace & 1) && tid == 0 && blockIdx.x < (unsigned)kMpmTraceItems) g_mpm_trace[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define PX_MPM_STAMP(i) do { } while (0)
-#endif
-
-// kernel variants (FL)
-constexpr int F_TRACE = 1;    // phase stamps + the ablation switches of StepParams.trace (timing studies only)
-constexpr int F_PACK32 = 2;   // packed 32-bit scatter (above)
-constexpr int F_WIDE = 8;     // no scheduling barriers: for scenes too small to fill the chip, where latency, not issue, binds
-
-// OCC = waves per SIMD the register allocation is held to (launch_bounds).  Built without the SLP vectoriser (see
-// pixie_amd/build.py) the kernel needs 96 VGPRs -> 5 waves per SIMD with no spills (with it: 168 VGPRs, 3 waves, and
-// 20 % slower); 6 -> 80 VGPRs with ~20 spilled dwords (measured slower: 86 vs 81 us at 1 M particles).  Chosen at run
-// time (set_scalar "occupancy"), same arithmetic.
-template <bool DO_G2P, bool DO_P2G, int OCC, int FL>
-__global__ __launch_bounds__(kWG, OCC) void mpm_block_kernel(MpmPtrs S, StepParams sp, PModSet pms) {
-    constexpr bool PACK = (FL & F_PACK32) != 0;
-    constexpr bool TRACE = (FL & F_TRACE) != 0;
-    constexpr bool SCHED = (FL & F_WIDE) == 0;
-    __shared__ float4 tv[kTN];    // grid velocities of the tile (G2P source)
-    __shared__ unsigned long long ta[PACK ? 2 : 4][kTN];  // (m*v.xyz, m) of this work item as scaled integers (P2G target)
-    __shared__ float s_red[2][kWG / 64];
-    // Workgroups are dealt to the 8 XCDs round-robin (workgroup b runs on XCD b % 8) and each XCD has its own L2.  The work list is in
-    // block order, so with sp.xcd_order every XCD takes a CONTIGUOUS eighth of it: neighbouring blocks -- whose 8^3 tiles of gout
-    // overlap eightfold -- then share their staging reads in that XCD's L2 instead of fetching them once per XCD
-    // (set_scalar "xcd_order", on by default: -2.6 % per substep at 1 M and 100 k, bit-identical results; the tile a work item
-    // publishes is addressed by the item, not by the workgroup).
-    int item = (int)blockIdx.x;
-    if (sp.xcd_order) {
-        const int per = (int)gridDim.x >> 3;
-        if (item < (per << 3)) item = (item & 7) * per + (item >> 3);      // (the last n % 8 items keep their place)
-    }
-#include "mpm_block_body.h"
-}
-
-// ------------------------------------------------------------------ re-binning (counting sort by block)
-__device__ __forceinline__ int block_of(const MpmPtrs& S, int p) {
-    int b[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        int base = (int)(S.x[d * S.n + p] * S.inv_dx - 0.5f);
-        base = max(0, min(base, S.ng - 3));
-        b[d] = base / kBS;
-    }
-    return (b[0] * S.nbk + b[1]) * S.nbk + b[2];
-}
-
-// key[p] = block of particle p; rank[p] = its arrival number inside the block.  Lanes of a wave that share a key
-// (the common case once the particles are binned) issue one atomic for the whole group.
-__global__ __launch_bounds__(256) void bin_count_kernel(MpmPtrs S, int* __restrict__ keys, int* __restrict__ rank,
-                                                        int* __restrict__ counts, unsigned* __restrict__ drift2_bits) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = p < S.n;
-    const int key = valid ? block_of(S, p) : -1;
-    {   // largest squared displacement since the last re-binning (drives the cadence, see rebin())
-        float d2 = 0.0f;
-        if (valid) {
-            for (int d = 0; d < 3; ++d) { const float e = S.x[d * S.n + p] - S.xref[d * S.n + p]; d2 += e * e; }
-            if (!(d2 < 3.0e38f)) d2 = 3.0e38f;
-        }
-        for (int off = 32; off > 0; off >>= 1) d2 = fmaxf(d2, __shfl_xor(d2, off, 64));
-        if ((threadIdx.x & 63) == 0 && d2 > __uint_as_float(*drift2_bits)) atomicMax(drift2_bits, __float_as_uint(d2));
-    }
-    // Two groups of a wave share one atomic each -- the key of its first lane and the key of the first lane outside that group (binned
-    // particles arrive block by block: a wave rarely spans more) -- and whoever is left takes its own.  All of a wave's atomics are
-    // then in flight within three round trips; until round 6 every distinct key of the wave cost a dependent one (a scene in motion:
-    // 4-6 per wave, 99 us for 1 M particles).  The arrival number is arbitrary either way; bin_local_order_kernel makes the order a
-    // function of the particle data.
-    const int lane = threadIdx.x & 63;
-    int my_rank = 0;
-    unsigned long long todo = __ballot(valid);
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int k = __shfl(key, leader);
-        const unsigned long long grp = __ballot(valid && key == k) & todo;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&counts[k], __popcll(grp));
-        base = __shfl(base, leader);
-        if ((grp >> lane) & 1ull) my_rank = base + __popcll(grp & ((1ull << lane) - 1ull));
-        todo &= ~grp;
-    }
-    if ((todo >> lane) & 1ull) my_rank = atomicAdd(&counts[key], 1);
-    if (valid) { keys[p] = key; rank[p] = my_rank; }
-}
-
-// Exclusive scan of the block counts + the work list (<= cap particles per item), in three launches over chunks of 1024 blocks:
-// chunk totals -> scan of the chunk totals (one workgroup) -> scan inside each chunk + the writes.  (Until round 5 ONE 1024-thread
-// workgroup walked all blocks: 58 us for the 27 000 blocks of a 120^3 grid, 280 us for the 125 000 of the reference's sand configuration
-// at n_grid 200 -- 7 % of that scene's run at a re-binning every ~33 substeps; profiles/r5last_stats_sand.csv.)
-constexpr int kScanChunk = 1024;
-struct ScanTriple { int cnt, itm, other; };   // particles, work items at `cap`, work items at the other capacity (auto item_cap, see rebin())
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-// exclusive prefix of v over the 1024-thread workgroup; *total = the workgroup's sum
-__device__ __forceinline__ int wg_excl_scan_1024(int v, int* s_wave /* [16] */, int* total) {
-    const int incl = wave_incl_scan(v);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) s_wave[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { const int t = s_wave[k]; if (k < w) base += t; tot += t; }
-    *total = tot;
-    return base + incl - v;
-}
-__device__ __forceinline__ ScanTriple scan_triple_of(int c, int cap) {
-    const int other = (cap == kWG) ? kWG / 2 : kWG;
-    return ScanTriple{c, (c + cap - 1) / cap, (c + other - 1) / other};
-}
-__global__ __launch_bounds__(kScanChunk) void bin_scan_partial_kernel(const int* __restrict__ counts, ScanTriple* __restrict__ chunk, int nblocks, int cap) {
-    __shared__ int s_w[3][16];
-    const int b = blockIdx.x * kScanChunk + threadIdx.x;
-    const ScanTriple t = scan_triple_of(b < nblocks ? counts[b] : 0, cap);
-    int v[3] = {t.cnt, t.itm, t.other};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-        if ((threadIdx.x & 63) == 0) s_w[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ScanTriple r{0, 0, 0};
-        for (int w = 0; w < 16; ++w) { r.cnt += s_w[0][w]; r.itm += s_w[1][w]; r.other += s_w[2][w]; }
-        chunk[blockIdx.x] = r;
-    }
-}
-// chunk totals -> exclusive prefixes (in place); n_items[0] = work items, n_items[3] = what the other capacity would make.  One workgroup.
-__global__ __launch_bounds__(1024) void bin_scan_chunks_kernel(ScanTriple* __restrict__ chunk, int nchunks, int* __restrict__ n_items) {
-    __shared__ int s_w[16];
-    const int per = (nchunks + 1023) / 1024;
-    const int c0 = min((int)threadIdx.x * per, nchunks), c1 = min(c0 + per, nchunks);
-    ScanTriple mine{0, 0, 0};
-    for (int c = c0; c < c1; ++c) { mine.cnt += chunk[c].cnt; mine.itm += chunk[c].itm; mine.other += chunk[c].other; }
-    int tc, ti, to;
-    int pc = wg_excl_scan_1024(mine.cnt, s_w, &tc);
-    int pi = wg_excl_scan_1024(mine.itm, s_w, &ti);
-    int po = wg_excl_scan_1024(mine.other, s_w, &to);
-    for (int c = c0; c < c1; ++c) {
-        const ScanTriple t = chunk[c];
-        chunk[c] = ScanTriple{pc, pi, po};
-        pc += t.cnt; pi += t.itm; po += t.other;
-    }
-    if (threadIdx.x == 0) { n_items[0] = ti; n_items[3] = to; }
-}
-__global__ __launch_bounds__(kScanChunk) void bin_scan_write_kernel(const int* __restrict__ counts, const ScanTriple* __restrict__ chunk,
-                                                                    int* __restrict__ offsets, int4* __restrict__ items,
-                                                                    int2* __restrict__ blk_items, int nblocks, int cap) {
-    __shared__ int s_w[16];
-    const int b = blockIdx.x * kScanChunk + threadIdx.x;
-    const int cnt = b < nblocks ? counts[b] : 0;
-    const int nit = (cnt + cap - 1) / cap;
-    const ScanTriple base = chunk[blockIdx.x];
-    int dummy;
-    const int c = base.cnt + wg_excl_scan_1024(cnt, s_w, &dummy);
-    int i = base.itm + wg_excl_scan_1024(nit, s_w, &dummy);
-    if (b >= nblocks) return;
-    offsets[b] = c;
-    blk_items[b] = make_int2(i, nit);
-    for (int j = 0; j < cnt; j += cap) items[i++] = make_int4(b, c + j, min(cap, cnt - j), 0);
-}
-
-__global__ __launch_bounds__(256) void bin_order_kernel(const int* __restrict__ keys, const int* __restrict__ rank,
-                                                        const int* __restrict__ offsets, int* __restrict__ order, int n) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < n) order[offsets[keys[p]] + rank[p]] = p;
-}
-
-// Order inside a block: round-robin over its 64 cells -- position = (rank within the cell, cell).  Consecutive lanes of
-// the block kernel then sit in consecutive cells, so the 27 same-offset LDS accesses of a wave (G2P reads and P2G
-// ds_add_u64) hit distinct nodes in distinct banks instead of colliding 3-4 ways as they do in arrival order.
-// One workgroup per block; `order` holds the block-contiguous listing, `order2` receives the final one.
-//
-// The rank within the cell is the particle's rank by its CURRENT SLOT among the block's particles of that cell -- not
-// its arrival number (`order` is filled through atomics, so arrival differs from run to run).  That makes the listing,
-// and with it the split of a crowded block into 256-particle work items and their fixed-point scales, a pure function
-// of the particle data: together with the integer tile sums and the fixed summation order of the grid kernel, a rollout
-// is bit-reproducible from run to run (as long as no particle takes the slow path's fp32 atomics).  Counting
-// "same cell, lower slot" is quadratic in the block's population -- cnt^2 / 256 compares per thread through LDS tiles,
-// ~20 us for the 800-particle blocks of the 100 k scene, once per re-binning.
-__device__ __forceinline__ int cell_in_block(const MpmPtrs& S, int p) {
-    int c = 0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        int base = (int)(S.x[d * S.n + p] * S.inv_dx - 0.5f);
-        base = max(0, min(base, S.ng - 3));
-        c = c * kBS + (base & (kBS - 1));
-    }
-    return c;
-}
-// Material class of a particle for the ordering inside a block: the constitutive branches of return_map_and_stress.  A block
-// that mixes materials (material_mode=neural uploads an id per particle, PG/material_field.py:343-363) is laid out class by
-// class, round-robin by cell inside a class, so that a wave runs ONE branch instead of all of them (mixed 1 M scene: 1955 -> 1600
-// VALU instructions per wave, 82.9 -> 78.5 us per substep = the single-material plastic scenes' 78.2; profiles/r5d_*); a
-// single-material block -- every block of a single-material scene -- keeps the order it always had.
-constexpr int kMatClasses = 7;
-__device__ __forceinline__ int material_class(int material) {
-    return material == 0 ? 0 : material == 1 ? 1 : material == 2 ? 2 : material == 3 ? 3 : material == 5 ? 4 : material == 6 ? 5 : 6;
-}
-__global__ __launch_bounds__(256) void bin_local_order_kernel(MpmPtrs S, const int* __restrict__ counts, const int* __restrict__ offsets,
-                                                              const int* __restrict__ order, int* __restrict__ cellk,
-                                                              int* __restrict__ rank, int* __restrict__ order2) {
-    constexpr int kCells = kBS * kBS * kBS;
-    __shared__ int cc[kMatClasses * kCells];     // particles per (class, cell)
-    __shared__ int s_class_base[kMatClasses];
-    __shared__ int2 s_tile[256];
-    const int b = blockIdx.x;
-    const int cnt = counts[b];
-    if (cnt == 0) return;
-    const int off = offsets[b];
-    for (int t = threadIdx.x; t < kMatClasses * kCells; t += 256) cc[t] = 0;
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-        const int p = order[off + t];
-        const int c = material_class(S.material[p]) * kCells + cell_in_block(S, p);   // key: (class, cell)
-        cellk[off + t] = c;
-        atomicAdd(&cc[c], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int m = 0; m < kMatClasses; ++m) {
-            s_class_base[m] = acc;
-            for (int k = 0; k < kCells; ++k) acc += cc[m * kCells + k];
-        }
-    }
-    __syncthreads();
-    for (int t0 = 0; t0 < cnt; t0 += 256) {
-        const int t = t0 + threadIdx.x;
-        const bool mine = t < cnt;
-        const int c = mine ? cellk[off + t] : -1, p = mine ? order[off + t] : 0;
-        int r = 0;
-        for (int u0 = 0; u0 < cnt; u0 += 256) {
-            __syncthreads();
-            const int u = u0 + threadIdx.x;
-            s_tile[threadIdx.x] = (u < cnt) ? make_int2(cellk[off + u], order[off + u]) : make_int2(-2, 0);
-            __syncthreads();
-            const int m = min(256, cnt - u0);
-            for (int k = 0; k < m; ++k) {
-                const int2 e = s_tile[k];
-                r += (e.x == c && e.y < p) ? 1 : 0;
-            }
-        }
-        if (mine) {      // slot = particles of earlier classes + (round r, cell) position inside the class
-            const int m = c / kCells, cl = c - m * kCells;
-            int pos = s_class_base[m];
-            for (int k = 0; k < kCells; ++k) {
-                const int n = cc[m * kCells + k];
-                pos += min(n, r) + ((k < cl && n > r) ? 1 : 0);
-            }
-            order2[off + pos] = p;
-        }
-    }
-}
-
-// blk_flags bit 0 <- "one of my 27 neighbours holds particles", and the compact list of those ACTIVE blocks: the only
-// ones the grid kernel is launched for (workgroup dispatch alone costs ~10 us for the 27000 blocks of a 120^3 grid).
-__global__ __launch_bounds__(256) void bin_mark_active_kernel(const int* __restrict__ counts, int* __restrict__ blk_flags,
-                                                              int* __restrict__ active_list, int* __restrict__ n_active, int nbk,
-                                                              const int2* __restrict__ blk_items, int2* __restrict__ nbr_table) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= nbk * nbk * nbk) return;
-    const int bz = b % nbk, by = (b / nbk) % nbk, bx = b / (nbk * nbk);
-    bool active = false;
-    for (int dx = -1; dx <= 1; ++dx)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dz = -1; dz <= 1; ++dz) {
-                const int x = bx + dx, y = by + dy, z = bz + dz;
-                if ((unsigned)x < (unsigned)nbk && (unsigned)y < (unsigned)nbk && (unsigned)z < (unsigned)nbk)
-                    active = active || counts[(x * nbk + y) * nbk + z] > 0;
-            }
-    blk_flags[b] = active ? 1 : 0;
-    if (!active) return;
-    const int slot = atomicAdd(n_active, 1);
-    active_list[slot] = b;
-    // everything the grid kernel needs to find this block's tiles, in one 224-byte row: one memory round trip there
-    // instead of active_list -> blk_items -> tiles
-    int2* row = nbr_table + (size_t)slot * 28;
-    row[0] = make_int2(b, 0);
-    for (int q = 0; q < 27; ++q) {
-        const int x = bx + q / 9 - 1, y = by + (q / 3) % 3 - 1, z = bz + q % 3 - 1;
-        const bool in = (unsigned)x < (unsigned)nbk && (unsigned)y < (unsigned)nbk && (unsigned)z < (unsigned)nbk;
-        row[1 + q] = in ? blk_items[(x * nbk + y) * nbk + z] : make_int2(0, 0);
-    }
-}
-
-// dst[r][q] = src[r][order[q]] for every row of the particle word array
-// `skip_vcft`: the launch this re-binning precedes starts with a G2P, which overwrites v, C and F_trial of every particle that takes
-// part (in the fused kernel they are not even stored between the gather and the scatter) -- 21 of the 51 rows are dead for those
-// particles and only travel for the ones that sit out (selection != 0: deselected by the caller or frozen outside the grid), whose
-// last stored values a caller may still read.
-__global__ __launch_bounds__(256) void bin_permute_kernel(const unsigned* __restrict__ src, unsigned* __restrict__ dst,
-                                                          const int* __restrict__ order, int n, int rows_per_y, int skip_vcft) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    const int p = order[q];
-    const int r0 = blockIdx.y * rows_per_y, r1 = min(r0 + rows_per_y, (int)R_COUNT);
-    const bool sits_out = skip_vcft && src[(size_t)R_SELECTION * n + p] != 0u;
-    for (int r = r0; r < r1; ++r) {
-        const bool dead = skip_vcft && ((r >= R_V && r < R_V + 3) || (r >= R_FT && r < R_FT + 9) || (r >= R_C && r < R_C + 9));
-        if (dead && !sits_out) continue;
-        const int rs = (r >= R_XREF) ? (R_X + r - R_XREF) : r;   // xref <- x: positions at this re-binning
-        dst[(size_t)r * n + q] = src[(size_t)rs * n + p];
-    }
-}
-
-__global__ void iota_kernel(int* dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = i;
-}
-
-// ------------------------------------------------------------------ grid kernel
-// grid_normalization_and_gravity (mpm_utils.py:398-409), add_damping_via_grid (:583-588) and the
-// BC `collide` closures (mpm_solver_warp.py:785-840 surface, :874-897 cuboid, :917-974 bounding box)
-// in one sweep; also re-zeroes (m*v, m) so the next P2G starts from a clean grid (zero_grid :295-300).
-// (No FMA contraction in apply_bc / finish_node: whether `float(k) * dx - point` is fused decides on which side of a collider plane a
-// node plane lies (tests: knife-edge scene), and hipcc's choice depends on the code around it.  Every operation rounded, as in the
-// float32 oracle -- the same bits in whatever kernel these are inlined into.)
-__device__ __forceinline__ void apply_bc(const BCDev& b, int ix, int iy, int iz, int ng, float dx, float time,
-                                         float dt, float v[3]) {
-#pragma clang fp contract(off)
-    if (b.type == PIXIE_BC_SURFACE) {
-        if (time >= b.start && time < b.end) {
-            const float ox = (float)ix * dx - b.point[0], oy = (float)iy * dx - b.point[1], oz = (float)iz * dx - b.point[2];
-            const float dp = ox * b.normal[0] + oy * b.normal[1] + oz * b.normal[2];
-            if (dp < 0.0f) {
-                if (b.surface_type == 11) {
-                    if ((float)iz * dx < 0.4f || (float)iz * dx > 0.53f) {
-                        v[0] = v[1] = v[2] = 0.0f;
-                    } else {
-                        v[0] = v[0] * 0.3f; v[1] = 0.0f; v[2] = v[2] * 0.3f;
-                    }
-                } else {
-                    // sticky, and -- as in the reference (:821-840) -- slip/friction too: the projected
-                    // velocity is computed there but the store is zero.
-                    v[0] = v[1] = v[2] = 0.0f;
-                }
-            }
-        }
-    } else if (b.type == PIXIE_BC_CUBOID) {
-        if (time >= b.start && time < b.end) {
-            const float ox = (float)ix * dx - b.point[0], oy = (float)iy * dx - b.point[1], oz = (float)iz * dx - b.point[2];
-            if (fabsf(ox) < b.size[0] && fabsf(oy) < b.size[1] && fabsf(oz) < b.size[2]) {
-                v[0] = b.velocity[0]; v[1] = b.velocity[1]; v[2] = b.velocity[2];
-            }
-        } else if (b.reset == 1) {
-            if (time < b.end + 15.0f * dt) v[0] = v[1] = v[2] = 0.0f;
-        }
-    } else {
-        const int padding = 3;
-        if (time >= b.start && time < b.end) {
-            if (ix < padding && v[0] < 0.0f) v[0] = 0.0f;
-            if (ix >= ng - padding && v[0] > 0.0f) v[0] = 0.0f;
-            if (iy < padding && v[1] < 0.0f) v[1] = 0.0f;
-            if (iy >= ng - padding && v[1] > 0.0f) v[1] = 0.0f;
-            if (iz < padding && v[2] < 0.0f) v[2] = 0.0f;
-            if (iz >= ng - padding && v[2] > 0.0f) v[2] = 0.0f;
-        }
-    }
-}
-
-// (m*v, m) of node (gx,gy,gz) = what slow-path particles added to gin + the tiles of the work items that cover the node.
-// A node with g = 4m + r along an axis lies in the tiles of blocks {m-1, m} (r < 3) or {m, m+1} (r = 3) on that axis:
-// 8 candidate blocks per node, all among the 27 neighbours of the node's own block.  The wave first fetches the 27
-// (first item, count) pairs with one load (lane i < 27), then every lane walks its 8 candidates in rounds so that the
-// 8 tile loads of a round are in flight together.  The order of the sum is fixed; every staged value is read once.
-// lane i < 27 fetches (first item, count) of neighbour block i of block (Bx,By,Bz); other lanes get (0,0)
-__device__ __forceinline__ int2 neighbour_items(const MpmPtrs& S, int Bx, int By, int Bz) {
-    const int lane = threadIdx.x & 63;
-    int2 mine = make_int2(0, 0);
-    if (lane < 27) {
-        const int bx = Bx + lane / 9 - 1, by = By + (lane / 3) % 3 - 1, bz = Bz + lane % 3 - 1;
-        if ((unsigned)bx < (unsigned)S.nbk && (unsigned)by < (unsigned)S.nbk && (unsigned)bz < (unsigned)S.nbk)
-            mine = S.blk_items[(bx * S.nbk + by) * S.nbk + bz];
-    }
-    return mine;
-}
-// One axis of staged_index: tile coordinate t -> (first node of its sub-box, nodes in the sub-box, t - first)
-__device__ __forceinline__ void staged_axis(int t, int& o, int& n, int& r) {
-    o = (t == 0) ? 0 : (t <= 4 ? 1 : 5);
-    n = (t == 0) ? 1 : (t <= 4 ? 4 : 3);
-    r = t - o;
-}
-// RB = items per candidate block fetched in one go (8 x RB tile loads in flight).
-//
-// Round 6: this gather was written as if the grid kernel were latency-bound, and its counters say otherwise -- 816 VALU instructions per
-// wave for ~10 float4 additions per lane: 3.7 waves per SIMD x 1.5 us of VALU issue at 1 M, FIFTEEN waves per SIMD on the reference's sand
-// configuration (15 700 active blocks: 21 of the launch's 21 us).  What it spent them on: staged_index per candidate (~30 selects x 8), a
-// branch + four zeroing moves around every predicated load, 64-bit address arithmetic, a 64-bit `live` word assembled bit by bit.  Now:
-// staged_index taken apart by axis (six small selects per axis and side, ~6 multiply-adds per candidate); 32-bit element offsets from
-// uniform bases; and NO predication -- a load that has nothing to fetch reads the all-zero tile at S.zero_off (or mask word 0, whose
-// value is then ignored), so every lane issues the same 8 x RB loads and adds what comes back.  Adding +0 changes nothing and the order of
-// the sum is still (round, candidate) whatever RB: every instantiation returns the bits it returned before.
-// (Round 4 tried issuing the first round's tile loads TOGETHER with the mask loads and dropping unstored nodes afterwards --
-// one dependent round trip fewer: 12.7 -> 15.5 us per launch at 1 M, the extra requests cost more than the trip saves;
-// profiles/r4f_mpm_grid_speculative_tile_loads_rejected.txt.  The loads added here all hit ONE line.)
-template <int RB>
-__device__ __forceinline__ float4 gather_node(const MpmPtrs& S, int2 mine, int lx, int ly, int lz, float4 acc) {
-    const int ax = (lx == 3) ? 0 : -1, ay = (ly == 3) ? 0 : -1, az = (lz == 3) ? 0 : -1;  // first candidate offset per axis
-    // this node inside the tiles of the two candidate blocks per axis: coordinates t0 and t0 - 4
-    const int t0x = lx - 4 * ax + 1, t0y = ly - 4 * ay + 1, t0z = lz - 4 * az + 1;
-    int ox[2], nx[2], rx[2], oy[2], ny[2], ry[2], oz[2], nz[2], rz[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        staged_axis(t0x - 4 * b, ox[b], nx[b], rx[b]);
-        staged_axis(t0y - 4 * b, oy[b], ny[b], ry[b]);
-        staged_axis(t0z - 4 * b, oz[b], nz[b], rz[b]);
-    }
-    const int src0 = (ax + 1) * 9 + (ay + 1) * 3 + (az + 1);
-    unsigned toff[8];  // in float4 units from S.part: first item * kTN + staged position of this node in that block's tiles
-    unsigned moff[8];  // in 32-bit words from S.tile_mask: first item * 16 + the word that holds this node's bit
-    int sh[8];         // ... and the bit inside it
-    int nit[8];        // items of the candidate block
-    int maxc = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int bx = c >> 2, by = (c >> 1) & 1, bz = c & 1;
-        const int src = src0 + bx * 9 + by * 3 + bz;
-        const int first = __shfl(mine.x, src), n = __shfl(mine.y, src);
-        const int bit = ((t0x - 4 * bx) * kTS + (t0y - 4 * by)) * kTS + (t0z - 4 * bz);
-        const int si = ox[bx] * 64 + nx[bx] * (oy[by] * 8 + ny[by] * oz[bz]) + (rx[bx] * ny[by] + ry[by]) * nz[bz] + rz[bz];   // = staged_index(tx, ty, tz)
-        toff[c] = (unsigned)first * kTN + (unsigned)si;
-        moff[c] = (unsigned)first * 16u + (unsigned)(bit >> 5);
-        sh[c] = bit & 31;
-        nit[c] = n;
-        maxc = max(maxc, n);
-    }
-    const unsigned* __restrict__ mask32 = reinterpret_cast<const unsigned*>(S.tile_mask);   // (little-endian halves of the 64-bit words)
-    const float4* __restrict__ part = S.part;
-    const unsigned zero = S.zero_off;
-    for (int r0 = 0; r0 < maxc; r0 += RB) {
-        unsigned idx[RB][8];
-        if (S.sparse_tiles) {                // (uniform)
-            unsigned w[RB][8];
-#pragma unroll
-            for (int r = 0; r < RB; ++r)
-#pragma unroll
-                for (int c = 0; c < 8; ++c) w[r][c] = mask32[(r0 + r < nit[c]) ? moff[c] + (unsigned)(r0 + r) * 16u : 0u];
-#pragma unroll
-            for (int r = 0; r < RB; ++r)
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const bool on = (r0 + r < nit[c]) && ((w[r][c] >> sh[c]) & 1u);
-                    idx[r][c] = on ? toff[c] + (unsigned)(r0 + r) * kTN : zero;
-                }
-        } else {
-#pragma unroll
-            for (int r = 0; r < RB; ++r)
-#pragma unroll
-                for (int c = 0; c < 8; ++c) idx[r][c] = (r0 + r < nit[c]) ? toff[c] + (unsigned)(r0 + r) * kTN : zero;
-        }
-        float4 q[RB][8];
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) q[r][c] = part[idx[r][c]];
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) { acc.x += q[r][c].x; acc.y += q[r][c].y; acc.z += q[r][c].z; acc.w += q[r][c].w; }
-    }
-    return acc;
-}
-
-// grid_normalization_and_gravity (mpm_utils.py:398-409), add_damping_via_grid (:583-588) and every BC for ONE node of block
-// (Bx,By,Bz), from its accumulated (m*v, m); returns grid_v_out
-__device__ __forceinline__ float4 finish_node(const MpmPtrs& S, const StepParams& sp, const BCSet& bcs, float4 g, int ix, int iy, int iz) {
-#pragma clang fp contract(off)
-    float v[3] = {0.0f, 0.0f, 0.0f};
-    if (g.w > 1e-15f) {
-        const float inv = 1.0f / g.w;
-        v[0] = g.x * inv + sp.dt * sp.g[0];
-        v[1] = g.y * inv + sp.dt * sp.g[1];
-        v[2] = g.z * inv + sp.dt * sp.g[2];
-    }
-    if (sp.do_damping) { v[0] *= sp.damping; v[1] *= sp.damping; v[2] *= sp.damping; }
-    for (int k = 0; k < bcs.n; ++k) apply_bc(bcs.bc[k], ix, iy, iz, S.ng, S.dx, sp.time, sp.dt, v);
-    return make_float4(v[0], v[1], v[2], 0.0f);
-}
-
-// One WAVE updates the 4x4x4 nodes of active block `slot`: gather the staged tiles (+ what slow-path particles added to gin),
-// normalise, gravity, damping, BCs -> dst.
-template <int RB>
-__device__ __forceinline__ void grid_block_update(const MpmPtrs& S, const StepParams& sp, const BCSet& bcs, int slot, float4* dst) {
-    const int lane = threadIdx.x & 63;
-#ifdef PIXIE_DIAG   // set_scalar "trace" 4: per active block four 100 MHz stamps -- start, neighbour row arrived, tiles summed, stored
-#define PX_GRID_STAMP(i) do { if ((sp.trace & 4) && lane == 0 && slot < kMpmTraceItems) { asm volatile("s_waitcnt vmcnt(0)"); g_mpm_trace[slot * 8 + (i)] = wall_clock64(); } } while (0)
-#else
-#define PX_GRID_STAMP(i) do { } while (0)
-#endif
-    PX_GRID_STAMP(0);
-    // one coalesced row: block id + the work items of the 27 neighbours (lane q holds neighbour q)
-    const int2 row = (lane < 28) ? S.nbr_table[(size_t)slot * 28 + lane] : make_int2(0, 0);
-    const int blk = __shfl(row.x, 0);
-    PX_GRID_STAMP(1);
-    int2 mine;
-    mine.x = __shfl(row.x, (lane + 1) & 63); mine.y = __shfl(row.y, (lane + 1) & 63);
-    const int Bz = blk % S.nbk, By = (blk / S.nbk) % S.nbk, Bx = blk / (S.nbk * S.nbk);
-    // bit 0: active (set at re-binning); bit 1: slow-path particles added fp32 atomics into gin here
-    const int flag = S.blk_flags[blk];
-    const int lx = lane >> 4, ly = (lane >> 2) & 3, lz = lane & 3;
-    const int ix = Bx * kBS + lx, iy = By * kBS + ly, iz = Bz * kBS + lz;
-    const bool inside = ix < S.ng && iy < S.ng && iz < S.ng;
-    const size_t idx = ((size_t)ix * S.ng + iy) * S.ng + iz;
-    float4 g = gather_node<RB>(S, mine, lx, ly, lz, make_float4(0.f, 0.f, 0.f, 0.f));   // does not wait for the flag
-    PX_GRID_STAMP(2);
-    if (flag & 2) {
-        if (inside) {
-            const float4 q = S.gin[idx];
-            g.x += q.x; g.y += q.y; g.z += q.z; g.w += q.w;
-            S.gin[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        if (lane == 0) S.blk_flags[blk] = flag & 1;
-    }
-    if (inside) dst[idx] = finish_node(S, sp, bcs, g, ix, iy, iz);
-    PX_GRID_STAMP(3);
-#ifdef PIXIE_DIAG
-    if ((sp.trace & 4) && lane == 0 && slot < kMpmTraceItems)
-        g_mpm_trace[slot * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
-#endif
-}
-
-// One wave per 4x4x4 block of nodes.  A block is ACTIVE when one of its 27 neighbours (itself included) holds particles.
-// Only active blocks are read by the next G2P (a tile reaches one block beyond its own), so inactive blocks are skipped
-// entirely (mode 0); their grid_v_out is brought up to date on demand (mode 1, used by the grid_v_out export) with the
-// parameters of the last update, which for a massless node is just the BCs on v = 0.
-// RB (tile loads in flight per candidate block) against occupancy.  The kernel is latency-bound -- a wave is three or four
-// dependent memory round trips -- so what counts is how many waves are resident: a scene with several work items per block
-// that fits in one round of waves (100 k particles in 50^3: 2200 active blocks) wants RB = 4 (189 VGPRs, 2 waves per SIMD); a
-// scene with ~1.2 items per block and 9000 active blocks (1 M in 120^3) wants the registers back: RB = 1 = 101 VGPRs = 4 waves
-// per SIMD, 14.9 -> 12.5 us per launch together with the sparse tiles.  (Holding the allocation to 80 / 64 VGPRs for 6 / 8 waves
-// spills 22 / 39 dwords: 20.4 / 25.5 us.  profiles/r3s_mpm_grid_kernel_occupancy.txt)
-// (Four active blocks per 256-thread workgroup instead of one wave per workgroup: measured equal at 3 700 active blocks in round 3 and again
-// at the 15 700 of the reference's sand configuration in round 6 -- 21.99 vs 21.0 us, 102.0 vs 101.8 us per substep; the launch is not
-// dispatch-bound.  profiles/r6c_sand_timing.txt)
-template <int RB>
-__global__ __launch_bounds__(64) void mpm_grid_block_kernel(MpmPtrs S, StepParams sp, BCSet bcs, int mode) {
-    if (mode == 0) {
-        grid_block_update<RB>(S, sp, bcs, (int)blockIdx.x, S.gout);
-        return;
-    }
-    const int blk = (int)blockIdx.x;
-    if (S.blk_flags[blk] & 1) return;
-    const int Bz = blk % S.nbk, By = (blk / S.nbk) % S.nbk, Bx = blk / (S.nbk * S.nbk);
-    const int lx = threadIdx.x >> 4, ly = (threadIdx.x >> 2) & 3, lz = threadIdx.x & 3;
-    const int ix = Bx * kBS + lx, iy = By * kBS + ly, iz = Bz * kBS + lz;
-    if (!(ix < S.ng && iy < S.ng && iz < S.ng)) return;
-    S.gout[((size_t)ix * S.ng + iy) * S.ng + iz] = finish_node(S, sp, bcs, make_float4(0.f, 0.f, 0.f, 0.f), ix, iy, iz);
-}
-
-// ------------------------------------------------------------------ several scenes per launch (pixie_mpm_batch_*)
-// A 100 k-particle scene gives one launch ~500 work items and ~2000 active blocks: too little to fill the chip, and each scene pays
-// its own two launches per substep.  The batched wrappers put the work items of up to kMaxBatch scenes into ONE block-kernel launch
-// and their active blocks into ONE grid-kernel launch, then run the solo kernels' own bodies on them.
-//
-// Where the per-scene parameters come from (kernel arguments would be ~2 KB per scene, and a copy per launch costs about what the
-// launch saves):
-//   * BatchScene, one per scene, in device memory: the scene's MpmPtrs, ALL its registered modifiers (impulses first -- the order of
-//     active_pmods; apply_pmod re-checks each window with the same float compare, so applying the inactive ones is a no-op), and
-//     pointers into this call's tables.  Written at the start of each pixie_mpm_batch_step and again after a re-binning of the scene
-//     (rebin() has just synchronised the stream: nothing in flight reads the old descriptor).
-//   * this call's tables, precomputed on the host at the start of the call and uploaded with the descriptors in ONE copy: the
-//     StepParams of every substep (only `time` advances) and the BCSet of every grid launch (moving cuboids advance in double on the
-//     host and are stored as float, advance_bcs_state) -- one BCSet for the whole call when the scene has no cuboid.
-//   * BatchLaunch, the kernel argument (~270 bytes): which scenes this launch covers and the prefix of their work items (or active
-//     blocks).  Everything that changes at a re-binning of one scene -- item counts, the capacity that groups launches -- is here.
-// The descriptor is read through an address-space-4 (constant) pointer with a wave-uniform scene index: scalar loads, as the solo
-// kernels' parameters are.  The block kernel copies MpmPtrs and StepParams into locals at entry: read through references the same
-// body was scheduled differently from the solo kernel and contracted other multiply-adds (F_trial differed in the last bit).
-constexpr int kMaxBatch = 32;
-struct BatchScene {
-    MpmPtrs S;
-    PModSet pms;                   // every registered modifier, impulses first
-    const StepParams* sp;          // [n_substeps + 1] of this call: the launch of `step` reads sp[step]
-    const unsigned char* bcs;      // BCSet records of this call's grid launches: grid launch `step` reads bcs + step * bc_stride
-    long long bc_stride;           // 0: no cuboid -- one record for the whole call
-};
-struct BatchLaunch {
-    const BatchScene* scenes;      // device descriptors
-    int n;                         // scenes in this launch
-    int step;                      // substep index into the call's tables
-    int xcd_order;                 // work items dealt to the XCDs in contiguous runs (as mpm_block_kernel)
-    int pad;
-    int scene[kMaxBatch];          // descriptor of launch scene k
-    int first[kMaxBatch + 1];      // first global work item (block kernel) / active block (grid kernel) of launch scene k
-};
-typedef const BatchScene __attribute__((address_space(4))) ConstBatchScene;
-
-// launch scene of global index `g` (wave-uniform: g is a workgroup index), and the descriptor it reads
-// (Launch: BatchLaunch, or ExportLaunch of the batched frame export)
-template <class Launch>
-__device__ __forceinline__ int batch_scene_of(const Launch& L, int g) {
-    int k = 0;
-    for (int j = 1; j < L.n; ++j) k += (g >= L.first[j]) ? 1 : 0;
-    return __builtin_amdgcn_readfirstlane(k);
-}
-// what a descriptor points at (this call's tables) is read the same way: through a constant-address-space view of the pointer
-template <class T>
-__device__ __forceinline__ const T& const_view(const T* p) {
-    return *(const T*)(const T __attribute__((address_space(4)))*)p;
-}
-template <class Launch>
-__device__ __forceinline__ const BatchScene& batch_desc(const Launch& L, int k) {
-    const ConstBatchScene* d = (const ConstBatchScene*)L.scenes + L.scene[k];
-    return *(const BatchScene*)d;
-}
-
-template <bool DO_G2P, bool DO_P2G, int OCC, int FL>
-__global__ __launch_bounds__(kWG, OCC) void mpm_block_batch_kernel(BatchLaunch BL) {
-    constexpr bool PACK = (FL & F_PACK32) != 0;     // (the prologue of mpm_block_kernel)
-    constexpr bool TRACE = (FL & F_TRACE) != 0;
-    constexpr bool SCHED = (FL & F_WIDE) == 0;
-    __shared__ float4 tv[kTN];
-    __shared__ unsigned long long ta[PACK ? 2 : 4][kTN];
-    __shared__ float s_red[2][kWG / 64];
-    // global work item (remapped over the XCDs like mpm_block_kernel's) -> (scene, the scene's own work item)
-    int item = (int)blockIdx.x;
-    if (BL.xcd_order) {
-        const int per = (int)gridDim.x >> 3;
-        if (item < (per << 3)) item = (item & 7) * per + (item >> 3);
-    }
-    const int k = batch_scene_of(BL, item);
-    const BatchScene& D = batch_desc(BL, k);
-    const MpmPtrs S = D.S;
-    const StepParams sp = const_view(D.sp + BL.step);
-    const PModSet& pms = D.pms;
-    item -= BL.first[k];
-#include "mpm_block_body.h"
-}
-
-template <int RB>
-__global__ __launch_bounds__(64) void mpm_grid_block_batch_kernel(BatchLaunch L) {
-    const int slot = (int)blockIdx.x;
-    const int k = batch_scene_of(L, slot);
-    const BatchScene& D = batch_desc(L, k);
-    const BCSet& bcs = const_view(reinterpret_cast<const BCSet*>(D.bcs + (size_t)L.step * (size_t)D.bc_stride));
-    grid_block_update<RB>(D.S, const_view(D.sp + L.step), bcs, slot - L.first[k], D.S.gout);
-}
-
-// export of grid_m / grid_v_in while a P2G is pending (tiles not yet consumed by the grid kernel)
-__global__ __launch_bounds__(64) void grid_export_pending_kernel(MpmPtrs S, float* __restrict__ out, int what) {
-    const int Bz = blockIdx.x % S.nbk, By = (blockIdx.x / S.nbk) % S.nbk, Bx = blockIdx.x / (S.nbk * S.nbk);
-    const int lx = threadIdx.x >> 4, ly = (threadIdx.x >> 2) & 3, lz = threadIdx.x & 3;
-    const int ix = Bx * kBS + lx, iy = By * kBS + ly, iz = Bz * kBS + lz;
-    const bool inside = ix < S.ng && iy < S.ng && iz < S.ng;
-    const size_t idx = ((size_t)ix * S.ng + iy) * S.ng + iz;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (inside) g = S.gin[idx];
-    g = gather_node<4>(S, neighbour_items(S, Bx, By, Bz), lx, ly, lz, g);
-    if (!inside) return;
-    if (what == 0) out[idx] = g.w;
-    else { out[3 * idx] = g.x; out[3 * idx + 1] = g.y; out[3 * idx + 2] = g.z; }
-}
-
-__global__ __launch_bounds__(256) void mpm_grid_kernel(MpmPtrs S, StepParams sp, BCSet bcs, int normalise) {
-    const long total = (long)S.ng * S.ng * S.ng;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int iz = (int)(idx % S.ng);
-    const int iy = (int)((idx / S.ng) % S.ng);
-    const int ix = (int)(idx / ((long)S.ng * S.ng));
-    float v[3] = {0.0f, 0.0f, 0.0f};
-    if (normalise) {
-        const float4 g = S.gin[idx];
-        if (g.w > 1e-15f) {
-            const float inv = 1.0f / g.w;
-            v[0] = g.x * inv + sp.dt * sp.g[0];
-            v[1] = g.y * inv + sp.dt * sp.g[1];
-            v[2] = g.z * inv + sp.dt * sp.g[2];
-        }
-        if (sp.do_damping) { v[0] *= sp.damping; v[1] *= sp.damping; v[2] *= sp.damping; }
-        if (g.x != 0.0f || g.y != 0.0f || g.z != 0.0f || g.w != 0.0f) S.gin[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    } else {
-        const float4 o = S.gout[idx];
-        v[0] = o.x; v[1] = o.y; v[2] = o.z;
-    }
-    for (int k = 0; k < bcs.n; ++k) apply_bc(bcs.bc[k], ix, iy, iz, S.ng, S.dx, sp.time, sp.dt, v);
-    S.gout[idx] = make_float4(v[0], v[1], v[2], 0.0f);
-}
-
-// ------------------------------------------------------------------ set-up / utility kernels
-__global__ void pmod_kernel(MpmPtrs S, StepParams sp, PModDev m) {  // overflow path (> kMaxPModFused modifiers)
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= S.n) return;
-    float x[3], v[3];
-    for (int d = 0; d < 3; ++d) { x[d] = S.x[d * S.n + p]; v[d] = S.v[d * S.n + p]; }
-    apply_pmod(m, S.perm[p], sp.time, sp.dt, S.mass[p], x, v);
-    for (int d = 0; d < 3; ++d) S.v[d * S.n + p] = v[d];
-}
-
-template <typename T>
-__global__ void aos_to_soa_kernel(const T* __restrict__ src, T* __restrict__ dst, int n, int k, const int* perm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = perm ? perm[i] : i;
-    for (int c = 0; c < k; ++c) dst[(size_t)c * n + i] = src[(size_t)s * k + c];
-}
-template <typename T>
-__global__ void soa_to_aos_kernel(const T* __restrict__ src, T* __restrict__ dst, int n, int k, const int* perm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = perm ? perm[i] : i;
-    for (int c = 0; c < k; ++c) dst[(size_t)s * k + c] = src[(size_t)c * n + i];
-}
-// selection 2 = "left the grid, frozen" (our marker; the reference has no such state): cleared when the caller replaces the
-// positions or re-makes the grid, so that particles that are inside again take part again
-__global__ void unfreeze_kernel(int* selection, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && selection[i] == 2) selection[i] = 0;
-}
-template <typename T>
-__global__ void fill_kernel(T* dst, long count, T value) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = value;
-}
-__global__ void identity_F_kernel(float* Ft, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int c = 0; c < 9; ++c) Ft[(size_t)c * n + i] = (c % 4 == 0) ? 1.0f : 0.0f;
-}
-// Smallest and largest positive particle mass (bit patterns of non-negative floats order like the floats).  The packed
-// scatter's quantum is 2^-30 of the SUM of a work item's contribution bounds, so a node fed only by particles R times lighter
-// than their neighbours in the tile is resolved to ~1e-6 R of its own mass: above a contrast of kPackMaxContrast
-// the exact 64-bit mode is selected instead.
-constexpr float kPackMaxContrast = 32.0f;
-__global__ void mass_range_kernel(MpmPtrs S, unsigned* __restrict__ range) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    float m = (p < S.n && S.selection[p] == 0) ? S.mass[p] : 0.0f;
-    unsigned lo = (m > 0.0f) ? __float_as_uint(m) : 0xffffffffu, hi = (m > 0.0f) ? __float_as_uint(m) : 0u;
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, off, 64));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { atomicMin(range, lo); atomicMax(range + 1, hi); }
-}
-
-__global__ void mass_kernel(MpmPtrs S) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < S.n) S.mass[i] = S.density[i] * S.vol[i];
-}
-// compute_mu_lam_from_E_nu / compute_bulk, mpm_utils.py:282-293
-__global__ void mu_lam_kernel(MpmPtrs S, int with_bulk) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const float E = S.E[i], nu = S.nu[i];
-    const float mu = E / (2.0f * (1.0f + nu));
-    const float lam = E * nu / ((1.0f + nu) * (1.0f - 2.0f * nu));
-    S.mu[i] = mu;
-    S.lam[i] = lam;
-    if (with_bulk) S.bulk[i] = lam + 2.f / 3.f * mu;
-}
-// apply_additional_params, mpm_utils.py:591-610
-__global__ void additional_params_kernel(MpmPtrs S, float3 pt, float3 sz, float E, float nu, float density, int material) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const float px = S.x[i], py = S.x[S.n + i], pz = S.x[2 * S.n + i];
-    if (px > pt.x - sz.x && px < pt.x + sz.x && py > pt.y - sz.y && py < pt.y + sz.y && pz > pt.z - sz.z && pz < pt.z + sz.z) {
-        S.E[i] = E; S.nu[i] = nu; S.density[i] = density; S.material[i] = material;
-    }
-}
-// The same for a list of boxes applied in order: every particle keeps the LAST box that contains it (what N sequential
-// launches of the kernel above leave behind).  Boxes are staged through LDS 256 at a time; the containment test is the
-// reference's float32 expression, box by box.
-__global__ __launch_bounds__(256) void additional_params_batch_kernel(MpmPtrs S, long n_boxes, const float* __restrict__ boxes,
-                                                                       const float* __restrict__ params, const int* __restrict__ material) {
-    __shared__ float sb[256][6];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < S.n;
-    const float px = valid ? S.x[i] : 0.0f, py = valid ? S.x[S.n + i] : 0.0f, pz = valid ? S.x[2 * S.n + i] : 0.0f;
-    long last = -1;
-    for (long b0 = 0; b0 < n_boxes; b0 += 256) {
-        const long mine = b0 + threadIdx.x;
-        __syncthreads();
-        if (mine < n_boxes)
-            for (int k = 0; k < 6; ++k) sb[threadIdx.x][k] = boxes[mine * 6 + k];
-        __syncthreads();
-        const int cnt = (int)min(256L, n_boxes - b0);
-        if (valid)
-            for (int j = 0; j < cnt; ++j) {
-                const float* q = sb[j];
-                if (px > q[0] - q[3] && px < q[0] + q[3] && py > q[1] - q[4] && py < q[1] + q[4] && pz > q[2] - q[5] && pz < q[2] + q[5]) last = b0 + j;
-            }
-    }
-    if (valid && last >= 0) {
-        S.E[i] = params[last * 3]; S.nu[i] = params[last * 3 + 1]; S.density[i] = params[last * 3 + 2]; S.material[i] = material[last];
-    }
-}
-// selection kernels, mpm_utils.py:613-663
-__global__ void select_kernel(MpmPtrs S, PModDev m, float3 size, float half_height, float radius, int* mask) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const float o[3] = {S.x[i] - m.point[0], S.x[S.n + i] - m.point[1], S.x[2 * S.n + i] - m.point[2]};
-    int sel;
-    if (m.type == PIXIE_PM_ROTATION) {
-        const float dn = o[0] * m.normal[0] + o[1] * m.normal[1] + o[2] * m.normal[2];
-        const float hx = o[0] - dn * m.normal[0], hy = o[1] - dn * m.normal[1], hz = o[2] - dn * m.normal[2];
-        sel = (fabsf(dn) < half_height && sqrtf(hx * hx + hy * hy + hz * hz) < radius) ? 1 : 0;
-    } else {
-        sel = (fabsf(o[0]) < size.x && fabsf(o[1]) < size.y && fabsf(o[2]) < size.z) ? 1 : 0;
-    }
-    mask[S.perm[i]] = sel;  // masks are kept in the caller's order
-}
-// compute_cov_from_F, mpm_utils.py:529-553
-__global__ void cov_kernel(MpmPtrs S, const float* __restrict__ init_cov, float* __restrict__ cov, const int* perm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const int s = perm ? perm[i] : i;
-    Mat3 F, M;
-    for (int c = 0; c < 9; ++c) F.m[c] = S.Ft[(size_t)c * S.n + i];
-    const float* c6 = init_cov + (size_t)s * 6;
-    M.m[0] = c6[0]; M.m[1] = c6[1]; M.m[2] = c6[2];
-    M.m[3] = c6[1]; M.m[4] = c6[3]; M.m[5] = c6[4];
-    M.m[6] = c6[2]; M.m[7] = c6[4]; M.m[8] = c6[5];
-    const Mat3 T = mat_mul_bt(mat_mul(F, M), F);
-    float* o = cov + (size_t)s * 6;
-    o[0] = T.m[0]; o[1] = T.m[1]; o[2] = T.m[2]; o[3] = T.m[4]; o[4] = T.m[5]; o[5] = T.m[8];
-}
-// Per-frame export for the rasteriser (PG/gs_simulation.py:591-600): positions and covariances of the first n_out
-// particles (caller order) in the original scene frame,
-//   pos_render = apply_inverse_rotations(undotransform2origin(undoshift2center111(x, z_shift), scale, mean), Rs)
-//   cov_render = apply_inverse_cov_rotations(compute_cov_from_F(F_trial, init_cov) / scale^2, Rs)
-// (PG/utils/transformation_utils.py:19-20,108-130; compute_cov_from_F mpm_utils.py:529-553) with the rotation chain
-// folded into one matrix M on the host: pos @ M, M^T cov M.  The body is shared textually with frame_export_batch_kernel.
-struct FrameXform { float shift[3]; float inv_scale; float mean[3]; float inv_scale2; float M[9]; };
-__global__ void frame_export_kernel(MpmPtrs S, const float* __restrict__ init_cov, FrameXform X, int n_out, float* __restrict__ pos_out,
-                                    float* __restrict__ cov_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-#include "frame_export_body.h"
-}
-// The same export for several scenes of a pixie_mpm_batch in one launch (pixie_mpm_batch_run): one record per scene in the call's
-// table (BatchExport), and a launch argument that says which scenes export which frame.  Block b of the launch belongs to launch
-// scene k with first[k] <= b < first[k + 1] (ceil(n / 256) blocks per scene, as frame_export_kernel's grid).
-struct BatchExport {
-    FrameXform X;
-    const float* init_cov;
-    float* pos;                    // frame 0 of [n_frames][n_out][3]
-    float* cov;                    // frame 0 of [n_frames][n_out][6], or NULL
-    int n_out;
-    int pad;
-};
-struct ExportLaunch {
-    const BatchScene* scenes;      // device descriptors (MpmPtrs kept current by batch_refresh)
-    const BatchExport* ex;         // export record of descriptor s: ex[s]
-    int n;                         // scenes in this launch
-    int pad;
-    int scene[kMaxBatch];          // descriptor of launch scene k
-    int frame[kMaxBatch];          // the frame launch scene k exports
-    int first[kMaxBatch + 1];      // first block of launch scene k
-};
-__global__ void frame_export_batch_kernel(ExportLaunch L) {
-    const int k = batch_scene_of(L, (int)blockIdx.x);
-    // (copied into locals first, as mpm_block_batch_kernel does: the body must see what frame_export_kernel's arguments give it)
-    const MpmPtrs S = batch_desc(L, k).S;
-    const BatchExport E = const_view(L.ex + L.scene[k]);
-    const FrameXform X = E.X;
-    const float* __restrict__ init_cov = E.init_cov;
-    const int n_out = E.n_out;
-    float* __restrict__ pos_out = E.pos + (size_t)L.frame[k] * (size_t)n_out * 3;
-    float* __restrict__ cov_out = E.cov ? E.cov + (size_t)L.frame[k] * (size_t)n_out * 6 : nullptr;
-    const int i = ((int)blockIdx.x - L.first[k]) * 256 + (int)threadIdx.x;
-#include "frame_export_body.h"
-}
-// The frame export with the 3DGS splat parameters of every exported covariance (PG/gs_simulation.py:290-322, the per-frame PLY):
-// frame_export_kernel's body, then splat::splat_from_cov of the covariance it has just stored (Rr, the values written to cov_out),
-// so the splats are the bits pixie_splat_from_cov gives for that cov.  Needs cov_out (the host refuses NULL).
-__global__ void frame_splat_kernel(MpmPtrs S, const float* __restrict__ init_cov, FrameXform X, int n_out, float* __restrict__ pos_out,
-                                   float* __restrict__ cov_out, float* __restrict__ log_scale_out, float* __restrict__ quat_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-#include "frame_export_body.h"
-    const float cs[6] = {Rr.m[0], Rr.m[1], Rr.m[2], Rr.m[4], Rr.m[5], Rr.m[8]};
-    float ls[3], qt[4];
-    splat::splat_from_cov(cs, ls, qt);
-    for (int d = 0; d < 3; ++d) log_scale_out[(size_t)s * 3 + d] = ls[d];
-    for (int d = 0; d < 4; ++d) quat_out[(size_t)s * 4 + d] = qt[d];
-}
-// Splat outputs of one scene in a pixie_mpm_batch_run_splats call: a record array of its own in the call's table, beside the
-// BatchExport records (indexed alike: descriptor s -> sp[s]).
-struct BatchSplat {
-    float* log_scale;              // frame 0 of [n_frames][n_out][3]
-    float* quat;                   // frame 0 of [n_frames][n_out][4]
-};
-// frame_export_batch_kernel's twin for the scenes that export splats (the same ExportLaunch, listing only those scenes)
-__global__ void frame_splat_batch_kernel(ExportLaunch L, const BatchSplat* __restrict__ sp) {
-    const int k = batch_scene_of(L, (int)blockIdx.x);
-    const MpmPtrs S = batch_desc(L, k).S;
-    const BatchExport E = const_view(L.ex + L.scene[k]);
-    const BatchSplat P = const_view(sp + L.scene[k]);
-    const FrameXform X = E.X;
-    const float* __restrict__ init_cov = E.init_cov;
-    const int n_out = E.n_out;
-    float* __restrict__ pos_out = E.pos + (size_t)L.frame[k] * (size_t)n_out * 3;
-    float* __restrict__ cov_out = E.cov + (size_t)L.frame[k] * (size_t)n_out * 6;
-    float* __restrict__ log_scale_out = P.log_scale + (size_t)L.frame[k] * (size_t)n_out * 3;
-    float* __restrict__ quat_out = P.quat + (size_t)L.frame[k] * (size_t)n_out * 4;
-    const int i = ((int)blockIdx.x - L.first[k]) * 256 + (int)threadIdx.x;
-#include "frame_export_body.h"
-    const float cs[6] = {Rr.m[0], Rr.m[1], Rr.m[2], Rr.m[4], Rr.m[5], Rr.m[8]};
-    float ls[3], qt[4];
-    splat::splat_from_cov(cs, ls, qt);
-    for (int d = 0; d < 3; ++d) log_scale_out[(size_t)s * 3 + d] = ls[d];
-    for (int d = 0; d < 4; ++d) quat_out[(size_t)s * 4 + d] = qt[d];
-}
-// cov3D_to_log_scales_and_quats (PG/gs_simulation.py:253-288) on its own: [n][6] -> [n][3], [n][4] (wxyz)
-__global__ void splat_from_cov_kernel(const float* __restrict__ cov, long n, float* __restrict__ log_scale_out, float* __restrict__ quat_out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float cs[6];
-    for (int d = 0; d < 6; ++d) cs[d] = cov[i * 6 + d];
-    float ls[3], qt[4];
-    splat::splat_from_cov(cs, ls, qt);
-    for (int d = 0; d < 3; ++d) log_scale_out[i * 3 + d] = ls[d];
-    for (int d = 0; d < 4; ++d) quat_out[i * 4 + d] = qt[d];
-}
-// compute_R_from_F, mpm_utils.py:556-580 (stores R^T)
-__global__ void rot_kernel(MpmPtrs S, float* __restrict__ Rout, const int* perm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const int s = perm ? perm[i] : i;
-    Mat3 F, U, V;
-    float sg[3];
-    for (int c = 0; c < 9; ++c) F.m[c] = S.Ft[(size_t)c * S.n + i];
-    svd3(F, U, sg, V);
-    const Mat3 R = mat_mul_bt(U, V);
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) Rout[(size_t)s * 9 + 3 * a + b] = R.m[3 * b + a];
-}
-// export_particle_stress_to_torch (mpm_solver_warp.py:691-692): the Kirchhoff stress of the stored,
-// return-mapped F -- what the last compute_stress_from_F_trial left in particle_stress.
-__global__ void stress_export_kernel(MpmPtrs S, float* __restrict__ out, const int* perm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n) return;
-    const int s = perm ? perm[i] : i;
-    Mat3 F;
-    for (int c = 0; c < 9; ++c) F.m[c] = S.F[(size_t)c * S.n + i];
-    const Mat3 tau = kirchhoff_stress(S.material[i], F, S.mu[i], S.lam[i], S.bulk[i]);
-    for (int c = 0; c < 9; ++c) out[(size_t)s * 9 + c] = tau.m[c];
-}
-__global__ void grid_export_kernel(const float4* __restrict__ g, float* __restrict__ out, long total, int what) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const float4 q = g[i];
-    if (what == 0) out[i] = q.w;
-    else { out[3 * i] = q.x; out[3 * i + 1] = q.y; out[3 * i + 2] = q.z; }
-}
-
 #ifdef PIXIE_DIAG
 int mpm_trace_read(unsigned long long* host, int n_words) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mpm_trace), (size_t)n_words * sizeof(unsigned long long));
@@ -1592,6 +65,20 @@ int mpm_trace_read(unsigned long long* host, int n_words) {
 
 // ====================================================================== host side
 using namespace pixie;
+
+// What a re-binning reads back (pinned; the copies of rebin() fill one group of fields each from its device-side producer)
+struct RebinReadback {
+    struct Counts {                      // d_n_items[0..3], as bin_scan_chunks_kernel / bin_mark_active_kernel / bin_count_kernel leave them
+        int n_items, n_active;
+        float drift2;                    // largest squared particle drift since the last re-binning
+        int n_items_other;               // work items at the other capacity (128 <-> 256)
+    } counts;
+    unsigned long long slow_total;       // oob[1]
+    struct { float lo, hi; } mass;       // d_mass_range[0..1]
+    unsigned long long left_grid;        // oob[0]
+    unsigned long long left_blocks;      // oob[2]
+};
+static_assert(sizeof(RebinReadback::Counts) == 4 * sizeof(int), "d_n_items is four 32-bit words");
 
 struct pixie_mpm {
     MpmPtrs S{};
@@ -1613,7 +100,7 @@ struct pixie_mpm {
     int nblocks = 0;
     int *keys = nullptr, *rank = nullptr, *counts = nullptr, *offsets = nullptr, *order = nullptr, *order2 = nullptr, *d_n_items = nullptr;
     int4* items = nullptr;
-    int* h_n_items = nullptr;                // pinned
+    RebinReadback* readback = nullptr;       // pinned
     int n_items = 0;
     bool needs_sort = true;                  // positions changed behind the binning's back (or never binned)
     int resort_interval = 4, steps_since_sort = 0;  // starts cautious, doubles while the measured drift allows
@@ -1671,12 +158,6 @@ int dev_alloc(pixie_mpm* h, T** ptr, size_t count, bool grid_sized = false) {
     return 0;
 }
 
-// The grid kernel runs one wave per active block.  Its RB = 4 instantiation fits two waves per SIMD: with more active blocks
-// than that (1 M particles in 120^3: ~2600 on 2048 slots) the launch takes a second round of waves and the leaner RB = 1
-// instantiation + sparse tiles win (14.9 -> 12.5 us); below it (100 k in 50^3: ~520) a launch is one wave's latency and the
-// fewer dependent loads the better (whole tiles, RB = 4: 18.7 vs 20.9 us per substep).
-bool grid_kernel_crowded(const pixie_mpm* h) { return h->n_active > 8 * h->n_cus; }
-
 // point the row pointers of h->S at the current copy of the word array
 void bind_rows(pixie_mpm* h) {
     MpmPtrs& S = h->S;
@@ -1716,6 +197,7 @@ int rebin(pixie_mpm* h, hipStream_t st, bool g2p_follows = false) {
     // Decided from the block histogram of THIS re-binning (both item counts come back with it; if the choice flips, only the work
     // list is built again -- three small launches): see below.
     h->item_cap = h->item_cap_user > 0 ? h->item_cap_user : (h->auto_half_items ? kWG / 2 : kWG);
+    RebinReadback* rb = h->readback;
     PX_CHECK_HIP(hipMemsetAsync(h->counts, 0, (size_t)h->nblocks * sizeof(int), st));
     PX_CHECK_HIP(hipMemsetAsync(h->d_n_items + 2, 0, sizeof(int), st));
     hipLaunchKernelGGL(bin_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, S, h->keys, h->rank, h->counts,
@@ -1734,73 +216,45 @@ int rebin(pixie_mpm* h, hipStream_t st, bool g2p_follows = false) {
         PX_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_mass_range, (int)0xffffffffu, 1, st));
         PX_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->d_mass_range + 1), 0, 1, st));
         hipLaunchKernelGGL(mass_range_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, S, h->d_mass_range);
-        PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items + 6, h->d_mass_range, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        PX_CHECK_HIP(hipMemcpyAsync(&rb->mass, h->d_mass_range, sizeof rb->mass, hipMemcpyDeviceToHost, st));
     }
-    PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items, h->d_n_items, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items + 4, h->S.oob + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items + 8, h->S.oob, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items + 10, h->S.oob + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    PX_CHECK_HIP(hipMemcpyAsync(&rb->counts, h->d_n_items, sizeof rb->counts, hipMemcpyDeviceToHost, st));
+    PX_CHECK_HIP(hipMemcpyAsync(&rb->slow_total, h->S.oob + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    PX_CHECK_HIP(hipMemcpyAsync(&rb->left_grid, h->S.oob, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    PX_CHECK_HIP(hipMemcpyAsync(&rb->left_blocks, h->S.oob + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     PX_CHECK_HIP(hipStreamSynchronize(st));
-    {   // particles lost so far (left the grid / left every active block), as of this re-binning: free to read, no extra sync
-        unsigned long long a, b;
-        memcpy(&a, h->h_n_items + 8, sizeof a); memcpy(&b, h->h_n_items + 10, sizeof b);
-        h->lost_seen = a + b;
-    }
-    h->n_items = h->h_n_items[0];
-    h->n_active = h->h_n_items[1];
+    // particles lost so far (left the grid / left every active block), as of this re-binning: free to read, no extra sync
+    h->lost_seen = rb->left_grid + rb->left_blocks;
+    h->n_items = rb->counts.n_items;
+    h->n_active = rb->counts.n_active;
     if (h->item_cap == kWG || h->item_cap == kWG / 2) {
-        // Half-size work items iff they would be nearly as few as full-size ones: enter at <= 15 % more, leave above 25 % (a scene
-        // near the threshold does not flip at every re-binning; the per-item fixed-point scale depends on the item size).
-        // (Break-even measured near +20 %: 1 M jelly in 200^3, +22 % items, 89.6 vs 90.6 us; the sand configuration, +2 ... 8 % over its
-        // run, 120 -> 108 us; dense scenes, +64 ... 74 % items, lose 13 %.  profiles/r5e_item_cap_sparse_scenes.txt)
-        const long other = h->h_n_items[3];
+        const long other = rb->counts.n_items_other;
         const long n256 = (h->item_cap == kWG) ? h->n_items : other, n128 = (h->item_cap == kWG) ? other : h->n_items;
-        if (!h->auto_half_items) h->auto_half_items = n128 * 100 <= n256 * 115;
-        else h->auto_half_items = n128 * 100 <= n256 * 125;
+        h->auto_half_items = half_items_wanted(h->auto_half_items, n128, n256);
         const int want = h->auto_half_items ? kWG / 2 : kWG;
         if (h->item_cap_user == 0 && want != h->item_cap) {   // in force from THIS binning: rebuild the work list for the other capacity
             h->item_cap = want;
             build_work_list(h, st);
-            PX_CHECK_HIP(hipMemcpyAsync(h->h_n_items, h->d_n_items, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+            PX_CHECK_HIP(hipMemcpyAsync(&rb->counts, h->d_n_items, 2 * sizeof(int), hipMemcpyDeviceToHost, st));   // (n_items, n_active)
             PX_CHECK_HIP(hipStreamSynchronize(st));
-            h->n_items = h->h_n_items[0];
-            h->n_active = h->h_n_items[1];
+            h->n_items = rb->counts.n_items;
+            h->n_active = rb->counts.n_active;
         }
     }
     if (measure_mass) {
-        float lo, hi;
-        memcpy(&lo, h->h_n_items + 6, sizeof lo); memcpy(&hi, h->h_n_items + 7, sizeof hi);
-        h->mass_contrast = (lo > 0.0f && hi >= lo && hi < 3.0e38f) ? hi / lo : 1.0f;
+        h->mass_contrast = mass_contrast_of(rb->mass.lo, rb->mass.hi);
         h->mass_range_dirty = false;
     }
     // (like sparse_tiles: decided at a re-binning only -- the mode changes how a tile is summed in LDS, not what is published)
-    h->scatter_bits = h->scatter_bits_user ? h->scatter_bits_user : (h->mass_contrast > kPackMaxContrast ? 64 : 32);
+    h->scatter_bits = scatter_bits_for(h->scatter_bits_user, h->mass_contrast);
     // (decided here and only here: never between a P2G and the grid kernel that consumes its tiles)
-    S.sparse_tiles = h->sparse >= 0 ? h->sparse : (grid_kernel_crowded(h) ? 1 : 0);
-    // Cadence: the LDS tile tolerates one cell of drift, and the measured drift of the interval just finished
-    // predicts the next one -- aim at 0.4 cells, never more than four times the last interval (a re-binning of 1 M
-    // particles costs ~0.4 ms = 4 substeps: with doubling, the ramp 4, 8, ..., 256 of a quiet scene spent six of them in
-    // the first 252 substeps), and halve when > 0.1 % of the particles were on the slow path.  (The host enqueues substeps
-    // far ahead of the device, so this is the only feedback.)  The 0.4 is not slack to be spent: aiming at 0.55 / 0.7 cells buys the
-    // reference's sand configuration 1 / 2 % (9 -> 6 re-binnings in 400 substeps) and costs a 100 k scene in motion 34 % / 183 % -- an
-    // accelerating scene overshoots the prediction and lands on the slow path (profiles/r6d_drift_target.txt).
+    S.sparse_tiles = h->sparse >= 0 ? h->sparse : (grid_crowded(h->n_active, h->n_cus) ? 1 : 0);
+    // Cadence from the measured drift and slow-path share of the interval just finished (next_resort_interval)
     if (h->resort_auto) {
-        unsigned long long slow_total;
-        memcpy(&slow_total, h->h_n_items + 4, sizeof slow_total);
-        const unsigned long long since = slow_total - h->slow_at_rebin;
-        h->slow_at_rebin = slow_total;
-        float d2;
-        memcpy(&d2, h->h_n_items + 2, sizeof d2);
-        const double drift_cells = sqrt((double)d2) * (double)S.inv_dx;
-        if (h->n_sorts > 0 && h->xref_valid) {
-            int k = h->resort_interval;
-            if (drift_cells > 0.0) k = (int)std::min<double>(4.0 * k, std::max<double>(0.25 * k, k * 0.4 / drift_cells));
-            else k = 4 * k;
-            if (since > (unsigned long long)n / 1000) k = std::min(k, h->resort_interval / 2);
-            // (ceiling 1024: a re-binning of 1 M particles is ~6 substeps' worth of time, so at 256 it still cost 2.6 % of a
-            // quiet scene's run; a scene that wakes up inside a long interval pays through the slow path until the next one)
-            h->resort_interval = std::max(2, std::min(k, 1024));
-        }
+        const unsigned long long since = rb->slow_total - h->slow_at_rebin;
+        h->slow_at_rebin = rb->slow_total;
+        const double drift_cells = sqrt((double)rb->counts.drift2) * (double)S.inv_dx;
+        if (h->n_sorts > 0 && h->xref_valid) h->resort_interval = next_resort_interval(h->resort_interval, drift_cells, since, n);
         h->xref_valid = true;
     }
     h->cur ^= 1;
@@ -1826,17 +280,6 @@ StepParams make_params(const pixie_mpm* h, double dt, double time) {
     return sp;
 }
 
-BCDev to_dev(const pixie_bc_desc& b) {
-    BCDev d{};
-    d.type = b.type; d.surface_type = b.surface_type; d.reset = b.reset;
-    for (int k = 0; k < 3; ++k) {
-        d.point[k] = (float)b.point[k]; d.size[k] = (float)b.size[k];
-        d.velocity[k] = (float)b.velocity[k]; d.normal[k] = (float)b.normal[k];
-    }
-    d.start = (float)b.start_time; d.end = (float)b.end_time; d.friction = (float)b.friction;
-    return d;
-}
-
 struct FieldInfo { void* ptr; int k; bool is_int; bool soa; };
 
 bool find_field(pixie_mpm* h, const std::string& name, FieldInfo* fi) {
@@ -1854,83 +297,48 @@ bool find_field(pixie_mpm* h, const std::string& name, FieldInfo* fi) {
     return false;
 }
 
-// The BCs of one launch, as the kernels take them
-BCSet make_bcset(const std::vector<BCDev>& bcs_dev, size_t first) {
-    BCSet set{};
-    set.n = (int)std::min<size_t>(kMaxBCPerLaunch, bcs_dev.size() - std::min(first, bcs_dev.size()));
-    for (int k = 0; k < set.n; ++k) set.bc[k] = bcs_dev[first + k];
-    return set;
-}
-BCSet make_bcset(const pixie_mpm* h, size_t first) { return make_bcset(h->bcs_dev, first); }
+BCSet make_bcset(const pixie_mpm* h, size_t first) { return pixie::make_bcset(h->bcs_dev, first); }
+void advance_bcs(pixie_mpm* h, double dt) { advance_bcs_state(h->time, h->bcs, h->bcs_dev, dt); }
+FusedVariant fused_variant(const pixie_mpm* h) { return pixie::fused_variant(h->wide, h->n_items, h->n_cus, h->occupancy, h->scatter_bits); }
 
-// host `modify` of moving cuboids (mpm_solver_warp.py:899-905) after the grid update of the substep at h->time:
-// python-float maths, stored as f32
-// (on explicit state: pixie_mpm_batch_step runs it ahead on copies to precompute a call's BC table)
-void advance_bcs_state(double time, std::vector<pixie_bc_desc>& bcs, std::vector<BCDev>& bcs_dev, double dt) {
-    for (size_t k = 0; k < bcs.size(); ++k) {
-        pixie_bc_desc& b = bcs[k];
-        if (b.type != PIXIE_BC_CUBOID) continue;
-        const double t0 = (double)(float)b.start_time, t1 = (double)(float)b.end_time;
-        if (time >= t0 && time < t1) {
-            for (int d = 0; d < 3; ++d) {
-                const float np = (float)((double)bcs_dev[k].point[d] + dt * (double)bcs_dev[k].velocity[d]);
-                bcs_dev[k].point[d] = np;
-                b.point[d] = np;
-            }
+// The one table of block-kernel variants: (g2p, p2g, fused variant, packed scatter, trace) -> the template arguments <G, P, OCC, FL>,
+// handed to launch.run<G, P, OCC, FL>().  The solo launch (mpm_block_kernel, below) and the batched one (mpm_block_batch_kernel,
+// mpm_batch_host.h) both read it: the variants round differently (test_latency_optimised_variant_matches), so a scene must get the
+// same one either way.  The F_TRACE pair (timing studies) exists for a Launch with kHasTrace in the PIXIE_DIAG build only.
+template <class Launch>
+void dispatch_block_variant(bool g2p, bool p2g, FusedVariant fv, bool pack, bool trace, const Launch& launch) {
+    if (g2p && p2g) {
+#ifdef PIXIE_DIAG
+        if constexpr (Launch::kHasTrace) {
+            if (trace && pack) return launch.template run<true, true, 5, F_TRACE | F_PACK32>();
+            if (trace) return launch.template run<true, true, 5, F_TRACE>();
         }
+#endif
+        if (fv == FV_WIDE && pack) launch.template run<true, true, 2, F_WIDE | F_PACK32>();
+        else if (fv == FV_WIDE) launch.template run<true, true, 2, F_WIDE>();
+        else if (fv == FV_SIX_WAVES) launch.template run<true, true, 6, 0>();
+        else if (pack) launch.template run<true, true, 5, F_PACK32>();
+        else launch.template run<true, true, 5, 0>();
+    } else if (g2p) {
+        launch.template run<true, false, 5, 0>();
+    } else if (pack) {
+        launch.template run<false, true, 5, F_PACK32>();
+    } else {
+        launch.template run<false, true, 5, 0>();
     }
 }
-void advance_bcs(pixie_mpm* h, double dt) { advance_bcs_state(h->time, h->bcs, h->bcs_dev, dt); }
 
-template <bool G, bool P, int OCC, int FL>
-void launch_block(const pixie_mpm* h, dim3 grid, hipStream_t st, const StepParams& sp, const PModSet& pms) {
-    hipLaunchKernelGGL((mpm_block_kernel<G, P, OCC, FL>), grid, dim3(h->item_cap), 0, st, h->S, sp, pms);
-}
-// exact (64-bit) or packed (32-bit pairs) scatter
-template <bool G, bool P, int OCC, int BASE>
-void launch_block_p(const pixie_mpm* h, bool pack, dim3 grid, hipStream_t st, const StepParams& sp, const PModSet& pms) {
-    if (pack) launch_block<G, P, OCC, BASE | F_PACK32>(h, grid, st, sp, pms);
-    else launch_block<G, P, OCC, BASE>(h, grid, st, sp, pms);
-}
-
-// Which fused G2P + P2G kernel the scene calls for (the variants differ in instruction order, not only in speed: a scene keeps its
-// variant in a batched launch too).  Latency-optimised variant (no scheduling barriers, 130 VGPRs = three waves per SIMD = three
-// 256-thread work items per CU at once): up to that many the whole work list is resident in one round and a launch lasts one work
-// item's latency.
-enum FusedVariant { FV_FIVE_WAVES = 0, FV_WIDE = 1, FV_SIX_WAVES = 2 };
-FusedVariant fused_variant(const pixie_mpm* h) {
-    const bool wide = h->wide == 1 || (h->wide < 0 && h->n_items <= 3 * h->n_cus);
-    if (wide) return FV_WIDE;
-    if (h->occupancy >= 6 && h->scatter_bits != 32) return FV_SIX_WAVES;   // six waves per SIMD: the exact scatter only (the one measured and tested)
-    return FV_FIVE_WAVES;
-}
-
-// the fused G2P + P2G launch in the variant the scene calls for
-void launch_fused_block(const pixie_mpm* h, hipStream_t st, const StepParams& sp, const PModSet& pms) {
-    const dim3 grid((unsigned)std::max(h->n_items, 1));
-    const bool pack = h->scatter_bits == 32;
-#ifdef PIXIE_DIAG
-    if (h->trace & ~4) { launch_block_p<true, true, 5, F_TRACE>(h, pack, grid, st, sp, pms); return; }
-#endif
-    const FusedVariant fv = fused_variant(h);
-    if (fv == FV_WIDE) launch_block_p<true, true, 2, F_WIDE>(h, pack, grid, st, sp, pms);
-    else if (fv == FV_SIX_WAVES) launch_block<true, true, 6, 0>(h, grid, st, sp, pms);
-    else launch_block_p<true, true, 5, 0>(h, pack, grid, st, sp, pms);
-}
-
-// particle modifiers whose window contains `time` (float compare, as the kernels do), impulses first (mpm_solver_warp.py:529-547);
-// `all`: every registered modifier in that order (the batched kernels, where apply_pmod checks the windows)
-std::vector<PModDev> active_pmods(const pixie_mpm* h, float time, bool all = false) {
-    std::vector<PModDev> ordered;
-    for (int pass = 0; pass < 2; ++pass)
-        for (size_t k = 0; k < h->pmods.size(); ++k) {
-            const PModDev& pm = h->pmods[k];
-            if ((pm.type == PIXIE_PM_IMPULSE) != (pass == 0)) continue;
-            if (!all && !(time >= pm.start && time < pm.end)) continue;
-            ordered.push_back(pm);
-        }
-    return ordered;
-}
+struct SoloBlockLaunch {
+    static constexpr bool kHasTrace = true;
+    const pixie_mpm* h;
+    hipStream_t st;
+    const StepParams& sp;
+    const PModSet& pms;
+    template <bool G, bool P, int OCC, int FL>
+    void run() const {
+        hipLaunchKernelGGL((mpm_block_kernel<G, P, OCC, FL>), dim3((unsigned)std::max(h->n_items, 1)), dim3(h->item_cap), 0, st, h->S, sp, pms);
+    }
+};
 
 // A substep's launches are split in two: the PLAN part (every decision and every change of host state: re-binning, cadence, modifier
 // selection, parameters, BC motion, time) and the ISSUE part (the launches).  pixie_mpm_step runs both per handle; pixie_mpm_batch_step
@@ -1951,7 +359,7 @@ int plan_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipStr
     if (g2p) ++h->steps_since_sort;
     pl.g2p = g2p; pl.p2g = p2g; pl.sp = sp; pl.pms = PModSet{};
     // modifiers whose time window cannot contain this substep are dropped on the host
-    pl.ordered = active_pmods(h, sp.time);
+    pl.ordered = active_pmods(h->pmods, sp.time);
     if (h->resort_auto && !pl.ordered.empty() && !h->pmods_were_active)   // a modifier switches on: velocities may jump
         h->resort_interval = std::min(h->resort_interval, 4);
     h->pmods_were_active = !pl.ordered.empty();
@@ -1970,26 +378,26 @@ int issue_particle(pixie_mpm* h, const ParticlePlan& pl, hipStream_t st) {
     const bool g2p = pl.g2p, p2g = pl.p2g;
     const StepParams& sp = pl.sp;
     const int blocks = cdiv(h->S.n, 256);
-    const dim3 grid((unsigned)std::max(h->n_items, 1));
-    const bool pack = h->scatter_bits == 32;
+    const bool pack = h->scatter_bits == 32, trace = (h->trace & ~4) != 0;
+    const FusedVariant fv = fused_variant(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->profile && p2g && g2p) {
         PX_CHECK_HIP(hipEventCreate(&e0)); PX_CHECK_HIP(hipEventCreate(&e1));
         PX_CHECK_HIP(hipEventRecord(e0, st));
     }
     if (g2p && p2g && pl.fused_mods) {
-        launch_fused_block(h, st, sp, pl.pms);
+        dispatch_block_variant(true, true, fv, pack, trace, SoloBlockLaunch{h, st, sp, pl.pms});
     } else {
         if (g2p) {
             PModSet none{};
-            launch_block<true, false, 5, 0>(h, grid, st, sp, none);
+            dispatch_block_variant(true, false, fv, pack, trace, SoloBlockLaunch{h, st, sp, none});
         }
         if (p2g) {
             if (!pl.fused_mods) {
                 for (const PModDev& m : pl.ordered)
                     hipLaunchKernelGGL(pmod_kernel, dim3(blocks), dim3(256), 0, st, h->S, sp, m);
             }
-            launch_block_p<false, true, 5, 0>(h, pack, grid, st, sp, pl.pms);
+            dispatch_block_variant(false, true, fv, pack, trace, SoloBlockLaunch{h, st, sp, pl.pms});
         }
     }
     if (e0) {
@@ -2007,7 +415,7 @@ int launch_particle(pixie_mpm* h, bool g2p, bool p2g, const StepParams& sp, hipS
 }
 
 void launch_grid_blocks(const pixie_mpm* h, hipStream_t st, const StepParams& sp, const BCSet& set, int mode, int n_wg) {
-    const int rb = h->grid_rb > 0 ? h->grid_rb : (grid_kernel_crowded(h) ? 1 : 4);
+    const int rb = h->grid_rb > 0 ? h->grid_rb : (grid_crowded(h->n_active, h->n_cus) ? 1 : 4);
     const dim3 g((unsigned)n_wg), b(64);
     if (rb == 1) hipLaunchKernelGGL(mpm_grid_block_kernel<1>, g, b, 0, st, h->S, sp, set, mode);
     else if (rb == 2) hipLaunchKernelGGL(mpm_grid_block_kernel<2>, g, b, 0, st, h->S, sp, set, mode);
@@ -2143,411 +551,7 @@ int alloc_grid(pixie_mpm* h, int n_grid, double grid_lim) {
 
 }  // namespace
 
-// Several scenes stepped with one block-kernel and one grid-kernel launch per substep (see BatchScene for the device side).
-struct pixie_mpm_batch {
-    std::vector<pixie_mpm*> h;
-    std::vector<MpmPtrs> desc_S;             // each scene's MpmPtrs as last uploaded (byte copies: compared with memcmp)
-    unsigned char* d_tab = nullptr;          // descriptors, then this call's StepParams tables and BCSet records
-    unsigned char* h_tab = nullptr;          // pinned staging image of d_tab for the current call: h_buf[cur_buf]
-    unsigned char* h_buf[2] = {nullptr, nullptr};   // two, used by alternate calls: a call waits only for the copies of the call before last
-    size_t cap = 0;
-    std::vector<size_t> sp_off;              // this window's StepParams table of scene s, in d_tab / h_tab
-    size_t ex_off = 0;                       // this call's export records (BatchExport per scene), if it exports
-    size_t spl_off = 0;                      // this call's splat records (BatchSplat per scene), if a scene exports splats
-    hipEvent_t ev_up[2] = {nullptr, nullptr};      // after the last copy out of h_buf[i] (h_buf[i] is rewritten only once it has run)
-    int cur_buf = 1;
-    int device = 0;                          // the HIP device current at creation: the events and tables live there
-    hipEvent_t finished = nullptr;           // after the last launch of the last call (d_tab is freed / reallocated only then)
-    int n_cus = 256;
-};
-
-namespace {
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// what a batched step does not cover (the fallbacks of launch_grid / launch_particle, the diagnostic kernels); checked before
-// anything is launched or changed
-int batch_check_handle(const pixie_mpm* h, int s, const char* what) {
-    PX_REQUIRE(!h->dirty_grid, "%s: scene %d has a phase-API P2G pending", what, s);
-    PX_REQUIRE(h->trace == 0, "%s: scene %d has `trace` set (the diagnostic kernels are not batched)", what, s);
-    PX_REQUIRE(h->bcs_dev.size() <= (size_t)kMaxBCPerLaunch, "%s: scene %d has %zu boundary conditions; a batched step takes at most %d per scene",
-               what, s, h->bcs_dev.size(), kMaxBCPerLaunch);
-    PX_REQUIRE(h->pmods.size() <= (size_t)kMaxPModFused, "%s: scene %d has %zu particle modifiers; a batched step takes at most %d per scene",
-               what, s, h->pmods.size(), kMaxPModFused);
-    return 0;
-}
-
-// One call's schedule for one scene (pixie_mpm_batch_run, validated): n_chunks chunks of `chunk` substeps of dt, the scene's
-// substep j being the call's global step j; `exp`: a frame export before every chunk (BatchExport record).
-struct BatchSched {
-    double dt = 0.0;
-    int chunk = 0;
-    int n_chunks = 0;
-    int total = 0;                 // chunk * n_chunks
-    bool exp = false;
-};
-
-// Long calls are tabled in windows of kBatchWindow global steps: a moving cuboid stores one BCSet record (up to ~1.4 KB) per substep,
-// and a 200-frame metal scene is 200 000 substeps.
-constexpr int kBatchWindow = 1024;
-
-// Start of a window [g0, g0 + kBatchWindow) of a call: the descriptors and the window's tables -- per scene, the StepParams of global
-// steps g0 ... g0 + n and the BCSet of grid launches g0 ... g0 + n - 1, n = the scene's substeps in the window -- are computed on the
-// host by running the solo step's own time / BC bookkeeping (make_params, make_bcset, advance_bcs_state) ahead on copies of the
-// handle's state, which the plans of the steps before g0 have brought to global step g0, and uploaded in one copy.  Launches index
-// the tables with the step relative to g0.  The plan of every substep checks what it computes against these tables (batch_expect_*).
-// `ex`: the call's export records, uploaded with every window (NULL: the call does not export); `spl` likewise its splat records
-// (NULL: no scene exports splats).
-int batch_upload(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, int g0, const std::vector<BatchExport>* ex,
-                 const std::vector<BatchSplat>* spl, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    std::vector<size_t> bc_off(ns), bc_stride(ns);
-    std::vector<int> n_win(ns);
-    b->sp_off.assign(ns, 0);
-    size_t off = align_up(sizeof(BatchScene) * ns, 256);
-    for (int s = 0; s < ns; ++s) {
-        n_win[s] = std::max(0, std::min(sc[s].total - g0, kBatchWindow));
-        b->sp_off[s] = off;
-        off = align_up(off + (size_t)(n_win[s] + 1) * sizeof(StepParams), 16);
-    }
-    const size_t head = offsetof(BCSet, bc);
-    for (int s = 0; s < ns; ++s) {
-        const pixie_mpm* h = b->h[s];
-        const size_t rec = align_up(head + h->bcs_dev.size() * sizeof(BCDev), 16);
-        bool moving = false;
-        for (const pixie_bc_desc& bc : h->bcs) moving = moving || bc.type == PIXIE_BC_CUBOID;
-        bc_stride[s] = moving ? rec : 0;
-        bc_off[s] = off;
-        off += moving ? rec * (size_t)n_win[s] : rec;
-    }
-    size_t ex_off = 0;
-    if (ex) {
-        ex_off = off = align_up(off, 16);
-        off += (size_t)ns * sizeof(BatchExport);
-    }
-    size_t spl_off = 0;
-    if (spl) {
-        spl_off = off = align_up(off, 16);
-        off += (size_t)ns * sizeof(BatchSplat);
-    }
-    // Rewriting d_tab between the windows of a call is safe without a synchronisation: the copy below is issued on `st`, the stream
-    // of every launch of the call, after the last launch of the previous window, and a launch of this window is issued after it.
-    // (The staging buffer is another matter: h_buf[cur_buf] is rewritten only once ev_up says its last copy has run.)
-    b->cur_buf ^= 1;
-    PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf]));   // the copies of the window before last (a no-op for an event never recorded)
-    if (off > b->cap) {
-        // launches of the last call may still read d_tab, and its copies may still read the other staging buffer.  (Within a call
-        // the first window is the largest -- scenes only drop out -- so this runs at g0 == 0; the stream synchronisation covers the
-        // call's own earlier launches otherwise.)
-        PX_CHECK_HIP(hipEventSynchronize(b->finished));
-        if (g0 > 0) PX_CHECK_HIP(hipStreamSynchronize(st));
-        PX_CHECK_HIP(hipEventSynchronize(b->ev_up[b->cur_buf ^ 1]));
-        if (b->d_tab) (void)hipFree(b->d_tab);
-        for (unsigned char*& hb : b->h_buf) { if (hb) (void)hipHostFree(hb); hb = nullptr; }
-        b->d_tab = nullptr; b->cap = 0;
-        const size_t cap = align_up(off + off / 2, 4096);
-        PX_CHECK_HIP(hipMalloc((void**)&b->d_tab, cap));
-        for (unsigned char*& hb : b->h_buf) PX_CHECK_HIP(hipHostMalloc((void**)&hb, cap));
-        b->cap = cap;
-    }
-    b->h_tab = b->h_buf[b->cur_buf];
-    b->desc_S.resize(ns);
-    for (int s = 0; s < ns; ++s) {
-        pixie_mpm* h = b->h[s];
-        BatchScene D;
-        memset(&D, 0, sizeof D);
-        memcpy(&D.S, &h->S, sizeof(MpmPtrs));
-        memcpy(&b->desc_S[s], &h->S, sizeof(MpmPtrs));
-        const std::vector<PModDev> all = active_pmods(h, 0.0f, true);
-        D.pms.n = (int)all.size();
-        for (int k = 0; k < D.pms.n; ++k) D.pms.pm[k] = all[k];
-        D.sp = reinterpret_cast<const StepParams*>(b->d_tab + b->sp_off[s]);
-        D.bcs = b->d_tab + bc_off[s];
-        D.bc_stride = (long long)bc_stride[s];
-        memcpy(b->h_tab + s * sizeof(BatchScene), &D, sizeof D);
-        const double dt = sc[s].dt;
-        double t = h->time;
-        std::vector<pixie_bc_desc> bcs = h->bcs;
-        std::vector<BCDev> bcs_dev = h->bcs_dev;
-        StepParams* spt = reinterpret_cast<StepParams*>(b->h_tab + b->sp_off[s]);
-        spt[0] = make_params(h, dt, t);
-        for (int i = 0; i < n_win[s]; ++i) {    // the order of pixie_mpm_step: grid launch at t, `modify`, t += dt, G2P/P2G at t
-            if (bc_stride[s] || i == 0) {
-                const BCSet set = make_bcset(bcs_dev, 0);
-                memcpy(b->h_tab + bc_off[s] + (size_t)i * bc_stride[s], &set, head + (size_t)set.n * sizeof(BCDev));
-            }
-            advance_bcs_state(t, bcs, bcs_dev, dt);
-            t = t + dt;
-            spt[i + 1] = make_params(h, dt, t);
-        }
-    }
-    b->ex_off = ex_off;
-    if (ex) memcpy(b->h_tab + ex_off, ex->data(), (size_t)ns * sizeof(BatchExport));
-    b->spl_off = spl_off;
-    if (spl) memcpy(b->h_tab + spl_off, spl->data(), (size_t)ns * sizeof(BatchSplat));
-    PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, off, hipMemcpyHostToDevice, st));
-    PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
-    return 0;
-}
-
-int batch_expect_sp(const pixie_mpm_batch* b, int s, int step, const StepParams& sp) {
-    const StepParams* spt = reinterpret_cast<const StepParams*>(b->h_tab + b->sp_off[s]);
-    PX_REQUIRE(memcmp(&spt[step], &sp, sizeof sp) == 0, "pixie_mpm_batch: scene %d: parameters of window step %d differ from the call's table (internal error)", s, step);
-    return 0;
-}
-int batch_expect_bcs(const pixie_mpm_batch* b, int s, int step, const BCSet& set) {
-    const BatchScene* D = reinterpret_cast<const BatchScene*>(b->h_tab) + s;
-    const unsigned char* rec = b->h_tab + (D->bcs - b->d_tab) + (size_t)step * (size_t)D->bc_stride;
-    PX_REQUIRE(memcmp(rec, &set, offsetof(BCSet, bc) + (size_t)set.n * sizeof(BCDev)) == 0,
-               "pixie_mpm_batch: scene %d: BCs of window step %d differ from the call's table (internal error)", s, step);
-    return 0;
-}
-
-// After the plan of a launch: a scene whose MpmPtrs changed (a re-binning: new row copy, sparse-tile mode) gets its descriptor
-// rewritten.  rebin() ends with a stream synchronisation, so nothing in flight reads the descriptors or copies out of h_tab;
-// the synchronisation below is that guarantee made explicit and costs nothing then.
-int batch_refresh(pixie_mpm_batch* b, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    bool changed = false;
-    for (int s = 0; s < ns; ++s) changed = changed || memcmp(&b->desc_S[s], &b->h[s]->S, sizeof(MpmPtrs)) != 0;
-    if (!changed) return 0;
-    PX_CHECK_HIP(hipStreamSynchronize(st));
-    for (int s = 0; s < ns; ++s) {
-        memcpy(&b->desc_S[s], &b->h[s]->S, sizeof(MpmPtrs));
-        memcpy(b->h_tab + s * sizeof(BatchScene) + offsetof(BatchScene, S), &b->h[s]->S, sizeof(MpmPtrs));
-    }
-    PX_CHECK_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, (size_t)ns * sizeof(BatchScene), hipMemcpyHostToDevice, st));
-    PX_CHECK_HIP(hipEventRecord(b->ev_up[b->cur_buf], st));
-    return 0;
-}
-
-template <bool G, bool P, int OCC, int FL>
-void launch_block_batch(const BatchLaunch& L, unsigned n_wg, int cap, hipStream_t st) {
-    hipLaunchKernelGGL((mpm_block_batch_kernel<G, P, OCC, FL>), dim3(n_wg), dim3((unsigned)cap), 0, st, L);
-}
-
-// One block-kernel launch per group of scenes that share a kernel variant: the launch kind (g2p, p2g) -- scenes at different points
-// of their schedules are fused, G2P-only (a chunk's last substep) or P2G-only (a chunk's first) at the same global step -- the
-// work-item capacity (blockDim), when the launch scatters the scatter mode, and for the fused launch each scene's own fused_variant
-// (the wide and the five-wave kernels round differently: test_latency_optimised_variant_matches).  The XCD remap does not change bits
-// and is chosen for the launch (on when every scene has it on).  Scenes whose plan has `run` unset take no part.
-int batch_issue_particle(pixie_mpm_batch* b, const std::vector<ParticlePlan>& pl, int step, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    std::vector<char> done(ns, 0);
-    for (int s0 = 0; s0 < ns; ++s0) {
-        if (done[s0] || !pl[s0].run) continue;
-        const pixie_mpm* h0 = b->h[s0];
-        const int cap = h0->item_cap;
-        const bool pack = h0->scatter_bits == 32;
-        const bool g2p = pl[s0].g2p, p2g = pl[s0].p2g;
-        const FusedVariant fv = fused_variant(h0);
-        BatchLaunch L;
-        memset(&L, 0, sizeof L);
-        L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
-        L.step = step;
-        L.xcd_order = 1;
-        long total = 0;
-        for (int s = s0; s < ns; ++s) {
-            const pixie_mpm* h = b->h[s];
-            if (done[s] || !pl[s].run || pl[s].g2p != g2p || pl[s].p2g != p2g) continue;
-            if (h->item_cap != cap || (p2g && (h->scatter_bits == 32) != pack)) continue;
-            if (g2p && p2g && fused_variant(h) != fv) continue;
-            done[s] = 1;
-            L.scene[L.n] = s;
-            L.first[L.n] = (int)total;
-            total += h->n_items;
-            if (!h->xcd_order) L.xcd_order = 0;
-            ++L.n;
-        }
-        PX_REQUIRE(total < (long)INT_MAX, "pixie_mpm_batch_step: %ld work items in one launch", total);
-        L.first[L.n] = (int)total;
-        const unsigned n_wg = (unsigned)total;
-        if (g2p && p2g) {
-            if (fv == FV_WIDE && pack) launch_block_batch<true, true, 2, F_WIDE | F_PACK32>(L, n_wg, cap, st);
-            else if (fv == FV_WIDE) launch_block_batch<true, true, 2, F_WIDE>(L, n_wg, cap, st);
-            else if (fv == FV_SIX_WAVES) launch_block_batch<true, true, 6, 0>(L, n_wg, cap, st);
-            else if (pack) launch_block_batch<true, true, 5, F_PACK32>(L, n_wg, cap, st);
-            else launch_block_batch<true, true, 5, 0>(L, n_wg, cap, st);
-        } else if (g2p) {
-            launch_block_batch<true, false, 5, 0>(L, n_wg, cap, st);
-        } else if (pack) {
-            launch_block_batch<false, true, 5, F_PACK32>(L, n_wg, cap, st);
-        } else {
-            launch_block_batch<false, true, 5, 0>(L, n_wg, cap, st);
-        }
-        PX_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
-}
-
-// One grid-kernel launch for every scene whose plan is the plain active-block update (every scene, given batch_check_handle: a
-// scene with staged tiles and <= kMaxBCPerLaunch BCs); anything else is issued as the solo step would.  RB from the launch's total.
-// Scenes with `on[s]` unset have no substep at this global step and take no part.
-int batch_issue_grid(pixie_mpm_batch* b, const std::vector<GridPlan>& gp, const std::vector<char>& on, int step, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    BatchLaunch L;
-    memset(&L, 0, sizeof L);
-    L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
-    L.step = step;
-    long total = 0;
-    for (int s = 0; s < ns; ++s) {
-        if (!on[s]) continue;
-        if (!gp[s].single_block_update()) {
-            if (issue_grid(b->h[s], gp[s], st)) return 1;
-            continue;
-        }
-        if (batch_expect_bcs(b, s, step, gp[s].ops[0].set)) return 1;
-        L.scene[L.n] = s;
-        L.first[L.n] = (int)total;
-        total += gp[s].ops[0].n_wg;
-        ++L.n;
-    }
-    if (L.n == 0) return 0;
-    PX_REQUIRE(total < (long)INT_MAX, "pixie_mpm_batch_step: %ld active blocks in one launch", total);
-    L.first[L.n] = (int)total;
-    const dim3 g((unsigned)total), blk(64);
-    if (total > 8L * b->n_cus) hipLaunchKernelGGL(mpm_grid_block_batch_kernel<1>, g, blk, 0, st, L);   // grid_kernel_crowded
-    else hipLaunchKernelGGL(mpm_grid_block_batch_kernel<4>, g, blk, 0, st, L);
-    PX_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// One frame_export_batch_kernel launch for every scene with frame[s] >= 0 (the frame it exports) and no splats, and one
-// frame_splat_batch_kernel launch for those with splats (splat[s]; empty: none has); none for an empty list.
-int batch_issue_export(pixie_mpm_batch* b, const std::vector<int>& frame, const std::vector<char>& splat, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    for (int with_splat = 0; with_splat < (splat.empty() ? 1 : 2); ++with_splat) {
-        ExportLaunch L;
-        memset(&L, 0, sizeof L);
-        L.scenes = reinterpret_cast<const BatchScene*>(b->d_tab);
-        L.ex = reinterpret_cast<const BatchExport*>(b->d_tab + b->ex_off);
-        long total = 0;
-        for (int s = 0; s < ns; ++s) {
-            if (frame[s] < 0 || (!splat.empty() && (splat[s] != 0) != (with_splat != 0))) continue;
-            L.scene[L.n] = s;
-            L.frame[L.n] = frame[s];
-            L.first[L.n] = (int)total;
-            total += cdiv(b->h[s]->S.n, 256);
-            ++L.n;
-        }
-        if (L.n == 0) continue;
-        L.first[L.n] = (int)total;
-        if (with_splat)
-            hipLaunchKernelGGL(frame_splat_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L,
-                               reinterpret_cast<const BatchSplat*>(b->d_tab + b->spl_off));
-        else
-            hipLaunchKernelGGL(frame_export_batch_kernel, dim3((unsigned)total), dim3(256), 0, st, L);
-        PX_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
-}
-
-// The launches of one call.  Every scene runs its chunks with the launch sequence of pixie_mpm_step -- a P2G-only launch, then per
-// substep [grid launch at t, t += dt, fused G2P + P2G, or G2P-only on the chunk's last substep] -- and its substep j is the call's
-// global step j, so the scenes that still have substeps share each global step's grid launch and particle launches (one per
-// variant group).  A scene that ends a chunk at a global step and has another one exports its next frame after that step's particle
-// launches -- its G2P-only launch has left v / C / F_trial valid (the note on skip_vcft); no export is ever issued inside a chunk,
-// frame_export reads F_trial -- and then plans and issues its next chunk's P2G-only launch, so that it joins the next grid launch.
-// Frame 0's export precedes everything.  Chunk boundaries are kept as given: each scene sees exactly the pixie_mpm_step calls
-// (and exports) of its solo loop, in the same order, on its own host state.
-// `spl`: per scene, where its splats go (BatchSplat, NULL pointers: none); empty when no scene exports splats.
-int batch_schedule(pixie_mpm_batch* b, const std::vector<BatchSched>& sc, const std::vector<BatchExport>& ex,
-                   const std::vector<BatchSplat>& spl, hipStream_t st) {
-    const int ns = (int)b->h.size();
-    int G = 0;
-    bool any_ex = false;
-    for (const BatchSched& q : sc) { G = std::max(G, q.total); any_ex = any_ex || q.exp; }
-    if (G == 0 && !any_ex) return 0;
-    const std::vector<BatchExport>* exr = any_ex ? &ex : nullptr;
-    std::vector<char> splat;               // which exporting scenes go through frame_splat_batch_kernel (empty: none)
-    for (int s = 0; s < (int)spl.size(); ++s)
-        if (sc[s].exp && spl[s].log_scale) { splat.assign(ns, 0); break; }
-    for (int s = 0; s < (int)splat.size(); ++s) splat[s] = sc[s].exp && spl[s].log_scale;
-    const std::vector<BatchSplat>* splr = splat.empty() ? nullptr : &spl;
-    int g0 = 0;
-    if (batch_upload(b, sc, g0, exr, splr, st)) return 1;
-    std::vector<ParticlePlan> pp(ns);
-    std::vector<GridPlan> gp(ns);
-    std::vector<char> on(ns, 0), next(ns, 0);
-    std::vector<int> frame(ns, -1);
-    // frame 0 of every exporting scene (a scene whose chunks are empty exports all its frames here, one launch per frame)
-    for (int f = 0; any_ex; ++f) {
-        bool any = false;
-        for (int s = 0; s < ns; ++s) {
-            const bool e = sc[s].exp && f < sc[s].n_chunks && (f == 0 || sc[s].chunk == 0);
-            frame[s] = e ? f : -1;
-            any = any || e;
-        }
-        if (!any) break;
-        if (batch_issue_export(b, frame, splat, st)) return 1;
-    }
-    // substep 0 of the first chunk: modifiers + stress + P2G at time t0
-    for (int s = 0; s < ns; ++s) {
-        pp[s].run = false;
-        if (sc[s].total == 0) continue;
-        pixie_mpm* h = b->h[s];
-        const StepParams sp = make_params(h, sc[s].dt, h->time);
-        if (batch_expect_sp(b, s, 0, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
-    }
-    if (batch_refresh(b, st) || batch_issue_particle(b, pp, 0, st)) return 1;
-    for (int g = 0; g < G; ++g) {
-        if (g - g0 == kBatchWindow) {
-            g0 = g;
-            if (batch_upload(b, sc, g0, exr, splr, st)) return 1;
-        }
-        const int i = g - g0;
-        for (int s = 0; s < ns; ++s) {
-            on[s] = g < sc[s].total;
-            if (!on[s]) continue;
-            pixie_mpm* h = b->h[s];
-            const StepParams sp = make_params(h, sc[s].dt, h->time);
-            if (batch_expect_sp(b, s, i, sp) || plan_grid(h, sp, sc[s].dt, gp[s])) return 1;
-        }
-        if (batch_issue_grid(b, gp, on, i, st)) return 1;
-        bool any_next = false;
-        for (int s = 0; s < ns; ++s) {
-            pp[s].run = false;
-            next[s] = 0;
-            frame[s] = -1;
-            if (!on[s]) continue;
-            pixie_mpm* h = b->h[s];
-            h->time = h->time + sc[s].dt;  // mpm_solver_warp.py:637
-            const bool last = (g + 1) % sc[s].chunk == 0;
-            const StepParams sp = make_params(h, sc[s].dt, h->time);
-            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, true, !last, sp, st, pp[s])) return 1;
-            if (last && g + 1 < sc[s].total) {
-                next[s] = 1;
-                any_next = true;
-                if (sc[s].exp) frame[s] = (g + 1) / sc[s].chunk;
-            }
-        }
-        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
-        if (!any_next) continue;
-        // scenes between two chunks: the next frame's export, then the next chunk's P2G-only launch at the same time
-        if (batch_issue_export(b, frame, splat, st)) return 1;
-        for (int s = 0; s < ns; ++s) {
-            pp[s].run = false;
-            if (!next[s]) continue;
-            pixie_mpm* h = b->h[s];
-            const StepParams sp = make_params(h, sc[s].dt, h->time);
-            if (batch_expect_sp(b, s, i + 1, sp) || plan_particle(h, false, true, sp, st, pp[s])) return 1;
-        }
-        if (batch_refresh(b, st) || batch_issue_particle(b, pp, i + 1, st)) return 1;
-    }
-    PX_CHECK_HIP(hipEventRecord(b->finished, st));
-    return 0;
-}
-
-// the export transform of pixie_mpm_export_frame / pixie_mpm_batch_run (float conversions of the caller's doubles)
-FrameXform make_frame_xform(const double shift[3], double scale, const double mean[3], const double inv_rotation[9]) {
-    FrameXform X{};
-    for (int d = 0; d < 3; ++d) { X.shift[d] = (float)shift[d]; X.mean[d] = (float)mean[d]; }
-    X.inv_scale = (float)(1.0 / scale); X.inv_scale2 = (float)(1.0 / (scale * scale));
-    for (int c = 0; c < 9; ++c) X.M[c] = (float)inv_rotation[c];
-    return X;
-}
-
-}  // namespace
+#include "mpm_batch_host.h"
 
 extern "C" {
 
@@ -2586,7 +590,7 @@ int pixie_mpm_create(pixie_mpm** out, int n_particles, int n_grid, double grid_l
     rc |= alloc_grid(h, n_grid, grid_lim);
     rc |= dev_alloc(h, &h->init_cov, 6 * n);
     if (rc) { pixie_mpm_destroy(h); return 1; }
-    if (hipHostMalloc((void**)&h->h_n_items, 12 * sizeof(int)) != hipSuccess) { pixie_mpm_destroy(h); return set_error("hipHostMalloc failed"); }
+    if (hipHostMalloc((void**)&h->readback, sizeof(RebinReadback)) != hipSuccess) { pixie_mpm_destroy(h); return set_error("hipHostMalloc failed"); }
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->n_cus = cus;
@@ -2608,7 +612,7 @@ int pixie_mpm_destroy(pixie_mpm* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     for (void* p : h->grid_allocs) (void)hipFree(p);
     for (int* m : h->masks) (void)hipFree(m);
-    if (h->h_n_items) (void)hipHostFree(h->h_n_items);
+    if (h->readback) (void)hipHostFree(h->readback);
     for (auto& e : h->ev_particle) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : h->ev_grid) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     delete h;

@@ -97,6 +97,23 @@ def test_variant_grouping(hip_device):
     assert int(batch[2]._get_scalar("item_cap")) == 256 and int(batch[3]._get_scalar("item_cap")) == 128
 
 
+def test_every_fused_variant_batched_equals_solo(hip_device):
+    """one scene per fused kernel variant -- wide + packed scatter, five waves + packed, wide + exact, six waves (exact only) -- in one
+    batch: the solo and the batched launch read one variant table (dispatch_block_variant), and the variants round differently, so a
+    scene that got another kernel in the batch would differ from its solo run"""
+    from pixie_amd.mpm_solver import SceneBatch
+    scs = [mpm_ball_scene(5_000, seed=70 + i, n_grid=32) for i in range(4)]
+    settings = [dict(wide=1), dict(wide=0), dict(wide=1, scatter_bits=64), dict(occupancy=6, scatter_bits=64, wide=0)]
+    setups = [lambda s, kv=kv: [s._set_scalar(k, v) for k, v in kv.items()] for kv in settings]
+    batch, alone = zip(*[pair(sc, st) for sc, st in zip(scs, setups)])
+    with SceneBatch(batch) as sb:
+        sb.run(DT, 30)
+        for i, (b, a) in enumerate(zip(batch, alone)):
+            a.run(DT, 30)
+            assert_same(b, a, f"scene {i} {settings[i]}")
+    assert [int(b._get_scalar("scatter_bits")) for b in batch] == [32, 32, 64, 64]
+
+
 def test_batch_of_one_equals_pixie_mpm_step(hip_device):
     from pixie_amd.mpm_solver import SceneBatch
     sc = mpm_ball_scene(30_000, seed=20, n_grid=40, scenario="tree")

@@ -83,6 +83,14 @@ __device__ __forceinline__ float act16(float t, int act) {
     if (act == 2) return t / (1.0f + __expf(-t));
     return t;
 }
+// The same values for the f16x3 staging (the exact-fp32 body keeps act16).  fmaxf(t, 0.02 t) is the LeakyReLU select bit for bit, for
+// +-0, +-inf and NaN too (t > 0: t > 0.02 t; t < 0: 0.02 t > t; at +-0 both operands are the same zero): one v_max_f32 for a compare
+// and a select.  The SiLU division stays IEEE: a denominator of +inf (t below about -88.7) gives -0.
+__device__ __forceinline__ float act16_staged(float t, int act) {
+    if (act == 1) return fmaxf(t, 0.02f * t);
+    if (act == 2) return t / (1.0f + __expf(-t));
+    return t;
+}
 // power-of-two scale that maps |x| <= bound to below 2^15 (fp16 max is 65504): s = 2^(14 - floor(log2 bound))
 __device__ __forceinline__ int scale_exponent(float bound) {
     const unsigned bits = __float_as_uint(bound);
@@ -300,17 +308,36 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         // affine (sub-pixel up-convs, 1x1x1, stride 2) are in profiles/conv_staging_{before,after}_kernel_stats_by_geometry.csv.
         const float* gsrc = has_aff ? A.gamma : A.in0;
         const float* bsrc = has_aff ? A.beta : A.in0;
+        // Addresses, as in the register-fed skip below: raw buffer loads over the chunk's first channel plane, the plane as the scalar
+        // offset, the slot's voxel as the 32-bit vector offset (the launcher checks that 16 planes span less than 4 GiB).  With 64-bit
+        // pointers an item pays 16 v_lshl_add_u64 and the 16 plane bases take 32 SGPRs.  Only where that lowers the registers: the
+        // 3^3 instantiations with 64 c_out per wave and two or four voxel blocks (<3,2,4>, c64_fullres, <3,2,2>: 2 - 3 VGPRs fewer,
+        // 3 - 5 % per launch); every other instantiation needs 6 - 17 VGPRs MORE with them (the descriptors and plane offsets
+        // overflow the scalar file into VGPR lanes) and <1,2,2>, <1,2,1>, <1,1,2> lose a wave of occupancy, so those keep the
+        // pointers.  A chunk that holds channels of both input tensors (c0 % 16 != 0; no layer of the networks)
+        // keeps the pointers too, in a plain loop of its own (pipeline): picking the resource per channel costs 11 - 15 VGPRs
+        // everywhere, and a branch around the loads spills at <3,2,4>.
+        constexpr bool BUF = KS == 3 && MB == 2 && NB >= 2 && !SP;
+        const unsigned chb = 4u * (unsigned)ISP;     // bytes per channel plane
+        const int j1 = A.c0 - c_base;                // the chunk's first channel that lies in in1 (<= 0: all of them, >= 16: none)
+        const bool straddle = j1 > 0 && j1 < 16;
+        const float* cbase = (j1 > 0) ? A.in0 + (size_t)c_base * ISP : A.in1 + (size_t)(c_base - A.c0) * ISP;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cbase), 0, -1, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gsrc), 0, -1, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bsrc), 0, -1, 0x00020000);
         struct Item { float val[16]; float gm, bt; bool ok; };
-        // geometry of the item at slot `vox`, then its loads; nothing here waits for memory
-        auto fetch = [&](Item& it, int vox) {
+        // geometry of the item at slot `vox`: whether it lies inside the input, and its element in a channel plane (outside: element 0)
+        auto slot = [&](int vox, bool& ok) {
             int rem = vox;
             const int hz = fast_div16(rem, A.HYX, A.mHYX);
             rem -= hz * A.HYX;
             const int hy = fast_div16(rem, A.HX, A.mHX);
             const int hx = rem - hy * A.HX;
             const int lz = lz0 + hz, ly = ly0 + hy, lx = lx0 + hx;
-            it.ok = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
-            const int sidx = it.ok ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
+            ok = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
+            return ok ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
+        };
+        auto load_with_pointers = [&](Item& it, int sidx) {
             it.gm = gsrc[sidx]; it.bt = bsrc[sidx];
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
@@ -318,27 +345,52 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
                 const float* src = (cg < A.c0) ? (A.in0 + (size_t)cg * ISP) : (A.in1 + (size_t)(cg - A.c0) * ISP);
                 it.val[j] = src[sidx];
             }
+        };
+        // the item's geometry, then its loads; nothing here waits for memory
+        auto fetch = [&](Item& it, int vox) {
+            const int sidx = slot(vox, it.ok);
+            if constexpr (BUF) {
+                const int voff = 4 * sidx;   // bytes into a plane
+                it.gm = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsg, voff, 0, 0));
+                it.bt = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsb, voff, 0, 0));
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    it.val[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff, (int)((unsigned)j * chb), 0));
+            } else {
+                load_with_pointers(it, sidx);
+            }
             // keep these loads above the conversion of the item before: left alone, the scheduler sinks them to their first use
             __builtin_amdgcn_sched_barrier(0);
         };
         auto convert = [&](const Item& it, int vox, auto has_pro, auto act_c) {
             const float gm = has_aff ? it.gm : 1.0f, bt = has_aff ? it.bt : 0.0f;
+            // Straight-line for every slot, the masked ones included (they hold element 0 of each plane): a select in front of the
+            // activation left SiLU one exec-masked block per element (s_and_saveexec, the full division, a wait of its own) and
+            // kept the hi / lo split from being packed.
             f16x8 vh[2], vl[2];
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 float t = it.val[j];
                 if (decltype(has_pro)::value) t = t * pa[j] + pb[j];
                 t = t * gm + bt;
-                const float sc = it.ok ? act16(t, decltype(act_c)::value) * sx : 0.0f;   // zero padding AFTER the activation
+                const float sc = act16_staged(t, decltype(act_c)::value) * sx;
                 const _Float16 h = (_Float16)sc;
                 vh[j >> 3][j & 7] = h;
                 vl[j >> 3][j & 7] = (_Float16)(sc - (float)h);
             }
+            // zero padding AFTER the activation: a select on the 8 + 8 packed words, whatever the masked slot computed (NaN, inf)
+            uint4 w[4] = {__builtin_bit_cast(uint4, vh[0]), __builtin_bit_cast(uint4, vh[1]), __builtin_bit_cast(uint4, vl[0]),
+                          __builtin_bit_cast(uint4, vl[1])};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                w[q].x = it.ok ? w[q].x : 0u; w[q].y = it.ok ? w[q].y : 0u;
+                w[q].z = it.ok ? w[q].z : 0u; w[q].w = it.ok ? w[q].w : 0u;
+            }
             if (vox < A.CS) {
-                bHi[vox] = __builtin_bit_cast(uint4, vh[0]);
-                bHi[A.CS + vox] = __builtin_bit_cast(uint4, vh[1]);
-                bLo[vox] = __builtin_bit_cast(uint4, vl[0]);
-                bLo[A.CS + vox] = __builtin_bit_cast(uint4, vl[1]);
+                bHi[vox] = w[0];
+                bHi[A.CS + vox] = w[1];
+                bLo[vox] = w[2];
+                bLo[A.CS + vox] = w[3];
             }
             __builtin_amdgcn_sched_barrier(0);   // the next fetch reuses this set: it stays below
         };
@@ -346,6 +398,16 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             Item a, b;
             int vox = stid;              // slot of the item in `a`; the one in `b` is nthr further on
             int left = n_items;          // items not yet converted, a's included
+            if constexpr (BUF) {
+                if (straddle) {          // one item at a time
+#pragma unroll 1
+                    for (; left > 0; --left, vox += nthr) {
+                        load_with_pointers(a, slot(vox, a.ok));
+                        convert(a, vox, has_pro, act_c);
+                    }
+                    return;
+                }
+            }
             fetch(a, vox);
 #pragma unroll 1
             for (; left > 2; left -= 2, vox += 2 * nthr) {
@@ -1375,6 +1437,8 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
     PX_REQUIRE(d->d_in_amax0 != nullptr || d->in_bound > 0.0f, "f16x3 conv: needs d_in_amax0 or a positive in_bound");
     PX_REQUIRE(d->c1 == 0 || d->d_in_amax0 == nullptr || d->d_in_amax1 != nullptr, "f16x3 conv: second input needs its own amax slot");
     PX_REQUIRE(p.refusal != CONV_BAD_SUBPIXEL, "f16x3 conv: sub-pixel weights need upsample = 1, ksize = 3, stride = 1 and no folded skip");
+    // the staging addresses a chunk's 16 channel planes with a 32-bit byte offset (raw buffer loads)
+    PX_REQUIRE((int64_t)d->in_d * d->in_h * d->in_w * 16 * (int64_t)sizeof(float) < (int64_t)1 << 32, "f16x3 conv: 16 channels of the input must span less than 4 GiB");
     Conv16Args a = conv16_args(d, p);
     a.w16 = reinterpret_cast<const uint4*>(d->d_w16);
     a.amax0 = d->d_in_amax0; a.amax1 = (d->c1 > 0) ? d->d_in_amax1 : nullptr; a.in_bound = d->in_bound;

@@ -793,7 +793,13 @@ int pixie_mpm_kernel_times(pixie_mpm* h, double* particle_ms, double* grid_ms, i
  * conv3d_f16x3_kernel<ksize,MB,NB> -- with a folded skip convolution: of conv3d_f16x3_skip_kernel<ksize,MB,NB,...>, the same
  * number -- (and its split-K factor in *slices), 9324 = conv3d_f16x3_c64_fullres_kernel (the <3,2,4>
  * code under its own symbol for the 64 -> 64 full-resolution 3^3 layers), 0 = the exact-fp32 kernel.  For profilers that
- * want to group per-launch timings by kernel name, as rocprofv3 does; no reference counterpart. */
+ * want to group per-launch timings by kernel name, as rocprofv3 does; no reference counterpart.
+ * The number does not say which launch form runs it: unsplit NB = 4 plans with an even number of 64-channel blocks and no folded skip
+ * are launched in pair form (conv3d_f16x3_pair_kernel<ksize,4>: 512 threads over one tile and 128 output channels, same results bit
+ * for bit).
+ * desc == NULL is the switch between the two forms, for tests and timings that need both from one build: *slices = 1 makes every
+ * following launch of this process keep the 4-wave kernels, *slices = 0 gives the choice back to the launcher, any other value (or
+ * slices == NULL) changes nothing; returns the setting before the call.  The product library has no such switch. */
 int pixie_conv_kernel_variant(const pixie_conv_desc* desc, int* slices);
 
 /* The tiling pixie_conv3d_forward launches this descriptor with, from the launchers' own selection code (a pure host function of
@@ -801,7 +807,10 @@ int pixie_conv_kernel_variant(const pixie_conv_desc* desc, int* slices);
  * tile being four (z, y)-parity workgroups), tiles_x, tiles_y, tiles_z, epi_lds (1 = the launch reserves LDS for the transposing
  * epilogue), slices (split-K factor), MB, NB.  With desc->d_w16 set it describes the f16x3 launch, otherwise the exact-fp32
  * launch of the same tiled body.  Returns 1 for descriptors that take neither (the first-generation exact kernel).  For tests that
- * must know which kernel variant and tile geometry a shape exercises. */
+ * must know which kernel variant and tile geometry a shape exercises.
+ * out == NULL asks for the launch form instead, from the launcher's own decision (a pure function of the plan and of whether a
+ * folded skip rides along): returns the dynamic LDS bytes of the pair-form launch, or 0 where the descriptor keeps the 4-wave
+ * kernel (always 0 while the switch of pixie_conv_kernel_variant is set). */
 int pixie_conv_tile_geometry(const pixie_conv_desc* desc, int32_t out[10]);
 /* Where this descriptor's launch leaves the partial statistics of desc->d_out_stats, from the code pixie_stats_finalize and
  * pixie_stats_norm_finalize read them with (a pure host function of the descriptor): out = n (partials per channel), cstride,

@@ -273,8 +273,8 @@ SIGNATURES = {
 DIAG_SIGNATURES = {
     "pixie_mpm_phase": (_I, [_VP, _I, _D, _VP]),
     "pixie_mpm_kernel_times": (_I, [_VP, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
-    "pixie_conv_kernel_variant": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),
-    "pixie_conv_tile_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
+    "pixie_conv_kernel_variant": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),     # (None, flag): the pair / 4-wave launch-form switch
+    "pixie_conv_tile_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),   # (desc, None): the launch form's LDS bytes, 0 = 4-wave
     "pixie_conv_stats_layout": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int64)]),
 }
 

@@ -119,8 +119,15 @@ __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned
 // block nb = 2 px + s holds x parity px of the wave's stored-voxel block s, so the transposing epilogue writes whole output
 // rows.  The tile is staged without the x2 replication with a halo of one voxel on the side the parity reads
 // (x: both sides), i.e. (TX + 2)(TY + 1)(TZ + 1) slots; A.ups is 0 and A.L* are the stored dims on this path.
-template <int KS, int MB, int NB, bool EX = false, bool SP = false, int SK = 0>
+// PAIR ("pair form", launches with an even number of 64-channel blocks): 512 threads = two quartets of 4 waves over ONE tile;
+// quartet q computes the c_out block 2 blockIdx.y + q and each of its waves is the 4-wave form's wave (same voxels, same A rows,
+// same order of chunks, taps and terms: the results are the 4-wave form's bit for bit).  The tile is staged once for both
+// quartets into two LDS buffers: chunk 0 by all 512 threads, then per chunk k quartet 0 stages its half of chunk k + 1's slots
+// and multiplies chunk k, quartet 1 multiplies first and stages afterwards, one barrier per chunk.  Waves w and w + 4 share a
+// SIMD, so each SIMD has one wave in the tap loop while the other stages.
+template <int KS, int MB, int NB, bool EX = false, bool SP = false, int SK = 0, bool PAIR = false>
 __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
+    static_assert(!PAIR || (MB == 2 && !EX && !SP && SK == 0), "pair form: the plain f16x3 body with 64 c_out per quartet");
     static_assert(!SP || (KS == 3 && NB == 4 && !EX), "sub-pixel path: 3^3, two x parities x two voxel blocks per wave");
     static_assert(SK == 0 || (!EX && !SP), "folded skip (SK: 1 register-fed, 2 staged through LDS): f16x3, no sub-pixel form");
     extern __shared__ uint4 smem16[];
@@ -130,7 +137,9 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int quartet = PAIR ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;   // wave-uniform
+    const int wave = PAIR ? (tid >> 6) & 3 : tid >> 6;                           // within the quartet
+    const int qtid = PAIR ? tid & 255 : tid;
     const int kh = lane >> 5;
     const int l31 = lane & 31;
 
@@ -150,7 +159,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     const int ty = t % A.tiles_y;
     const int tz = t / A.tiles_y;
     const int ox0 = tx * A.TX, oy0 = ty * A.TY, oz0 = tz * A.TZ;   // SP: in stored voxels
-    const int cout0 = blockIdx.y * (MB * 32);
+    const int cout0 = (PAIR ? 2 * (int)blockIdx.y + quartet : (int)blockIdx.y) * (MB * 32);
     const int lx0 = SP ? ox0 - 1 : ox0 * A.stride - PAD;
     const int ly0 = SP ? oy0 - 1 + py : oy0 * A.stride - PAD;
     const int lz0 = SP ? oz0 - 1 + pz : oz0 * A.stride - PAD;
@@ -213,7 +222,8 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
 
     constexpr int TAPS = KS * KS * KS;
     // ---- stage the 16-channel chunk starting at c_base into `buf`: one voxel x 16 channels per item.  A thread owns the items
-    // k = 0 .. n - 1 at slots stid + nthr k, n = ceil(CS / nthr) (workgroup-uniform; 5 at the 34 x 6 x 6 tile), and walks them as a
+    // k = 0 .. n - 1 at slots s0 + stid + nthr k of the slot range [s0, s1), n = ceil((s1 - s0) / nthr) (uniform over the staging
+    // threads; the 4-wave form stages [0, CS) with all its threads: 5 at the 34 x 6 x 6 tile), and walks them as a
     // rotating pipeline over two register sets: the 16 + 2 loads of item k + 1 are issued -- behind its geometry, which is computed
     // under the flight of item k -- before item k is converted and written, so a chunk exposes ONE global-memory round trip and
     // every later conversion waits with a counted vmcnt while the younger item is in flight.  The loop is unrolled by two so that
@@ -226,7 +236,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     // issue back to back without exec-mask branches, and the (has-prologue, activation) switch selects one of six
     // straight-line pipelines.  (The first version left those decisions to per-element code; the compiler
     // turned the constants into dependent vector loads with s_waitcnt vmcnt(0) -- 16 of the 27 us a chunk took.)
-    auto stage_chunk = [&](int c_base, uint4* buf, int stid, int nthr) {
+    auto stage_chunk = [&](int c_base, uint4* buf, int stid, int nthr, int s0, int s1) {
         uint4* bHi = buf;
         uint4* bLo = buf + 2 * A.CS;
         float pa[16], pb[16];
@@ -299,7 +309,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             }
             return;
         }
-        const int n_items = (A.CS + nthr - 1) / nthr;
+        const int n_items = (s1 - s0 + nthr - 1) / nthr;
         // The LayerNorm affine is fetched FIRST and without a branch (no affine: any readable element, replaced by 1 and 0 in the
         // conversion): every element's conversion needs it, and a load that may or may not have been issued behind the older
         // item's would turn that item's counted wait into one that also drains the head of the younger.  Without an affine the two
@@ -334,7 +344,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             const int hy = fast_div16(rem, A.HX, A.mHX);
             const int hx = rem - hy * A.HX;
             const int lz = lz0 + hz, ly = ly0 + hy, lx = lx0 + hx;
-            ok = vox < A.CS && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
+            ok = vox < s1 && (unsigned)lz < (unsigned)A.LD && (unsigned)ly < (unsigned)A.LH && (unsigned)lx < (unsigned)A.LW;
             return ok ? ((lz >> A.ups) * A.IH + (ly >> A.ups)) * A.IW + (lx >> A.ups) : 0;
         };
         auto load_with_pointers = [&](Item& it, int sidx) {
@@ -386,7 +396,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
                 w[q].x = it.ok ? w[q].x : 0u; w[q].y = it.ok ? w[q].y : 0u;
                 w[q].z = it.ok ? w[q].z : 0u; w[q].w = it.ok ? w[q].w : 0u;
             }
-            if (vox < A.CS) {
+            if (vox < s1) {
                 bHi[vox] = w[0];
                 bHi[A.CS + vox] = w[1];
                 bLo[vox] = w[2];
@@ -396,7 +406,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         };
         auto pipeline = [&](auto has_pro, auto act_c) {
             Item a, b;
-            int vox = stid;              // slot of the item in `a`; the one in `b` is nthr further on
+            int vox = s0 + stid;         // slot of the item in `a`; the one in `b` is nthr further on
             int left = n_items;          // items not yet converted, a's included
             if constexpr (BUF) {
                 if (straddle) {          // one item at a time
@@ -593,11 +603,36 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     {
         const int c_begin = A.partial ? (int)blockIdx.z * A.chunks_per_slice * 16 : 0;
         const int c_end = A.partial ? min(A.cin, c_begin + A.chunks_per_slice * 16) : A.cin;
+        if constexpr (PAIR) {
+            // Half-steps.  A quartet always stages its own half of a chunk's slots, [0, half) or [half, CS): at h = -1 both stage
+            // chunk 0, which so is staged by all 512 threads; after that a quartet alternates between staging its half of the
+            // next chunk and multiplying the chunk in hand, quartet 0 staging first, and every odd h ends in the barrier.  Chunk
+            // c lives in buffer c & 1: it is written during iteration c - 1, while both quartets read buffer (c - 1) & 1, and read
+            // during iteration c.
+            // One copy of each phase, under two guards of their own.  Measured by cross-compilation, <3,2,4> / <3,2,2> VGPRs
+            // (4-wave twins: 253 / 172): this form 249 / 175; `if (stage) ... else ...` in the same loop 256 and 244 spilled /
+            // 232; a second copy of stage_chunk for chunk 0 (all threads over [0, CS)) in front of either loop 256 / 248-250 and
+            // the epilogue's scalar pins no longer compile; the staging thread count and slot range as loop-carried variables
+            // 253 and 244 spilled / 230.
+            const int n_chunks = (c_end - c_begin) >> 4;
+            const int half = (A.CS + 1) >> 1;
+            const int s0 = quartet ? half : 0, s1 = quartet ? A.CS : half;
+#pragma unroll 1
+            for (int h = -1; h < 2 * n_chunks; ++h) {
+                const int k = h >> 1;                       // the chunk in hand (-1 before the first)
+                const bool stage = (h < 0 || ((h + quartet) & 1) == 0) && k + 1 < n_chunks;
+                const bool multiply = h >= 0 && ((h + quartet) & 1) != 0;
+                if (stage) stage_chunk(c_begin + 16 * (k + 1), smem16 + ((k + 1) & 1) * bufsz, qtid, NT, s0, s1);
+                if (multiply) mfma_chunk(c_begin + 16 * k, smem16 + (k & 1) * bufsz);
+                if (h & 1) __syncthreads();
+            }
+        } else {
         for (int c_base = c_begin; c_base < c_end; c_base += 16) {
             __syncthreads();  // previous chunk fully consumed
-            stage_chunk(c_base, smem16, tid, NT);
+            stage_chunk(c_base, smem16, tid, NT, 0, A.CS);
             __syncthreads();
             mfma_chunk(c_base, smem16);
+        }
         }
         if constexpr (SK != 0) {
             // ---- the block's 1x1x1 skip convolution, in the same accumulators (so that out = conv(h) + skip(x) leaves this
@@ -787,7 +822,11 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
             }
         return;
     }
-    float* red = reinterpret_cast<float*>(smem16);   // [4 waves][MB*32 rows][2], reused after the last chunk
+    // [4 waves][MB*32 rows][2], reused after the last chunk.  Pair form: one such array per quartet, behind the eight waves'
+    // transposing area where the launch reserved one -- the quartets of a tile may take different epilogue paths (a partly padded
+    // second block), so the place cannot depend on the path.
+    constexpr int LDO_ = NB * 32 + 4;
+    float* red = reinterpret_cast<float*>(smem16) + (PAIR ? (A.epi_lds ? 2 * NW * 32 * LDO_ : 0) + quartet * (NW * MB * 64) : 0);
     float wmax = 0.0f;
     // workgroup-uniform: every accumulator element of this tile is a real output
     const bool full = SP ? (A.epi_lds && cout0 + MB * 32 <= A.cout && (A.TX & 1) == 0 && (A.OW & 3) == 0 && NW * 64 <= A.TX * A.TY * A.TZ &&
@@ -805,8 +844,8 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         // of the barrier, the residual a group of four rows ahead of the stores, and (residual, statistics) select one of
         // four straight-line bodies.)
         constexpr int LDO = NB * 32 + 4;                                  // row stride in floats
-        float* ldsO = reinterpret_cast<float*>(smem16) + wave * (32 * LDO);   // this wave's 32 rows; no other wave touches it
-        red = reinterpret_cast<float*>(smem16) + NW * 32 * LDO;
+        float* ldsO = reinterpret_cast<float*>(smem16) + (quartet * NW + wave) * (32 * LDO);   // this wave's 32 rows; no other wave touches it
+        if constexpr (!PAIR) red = reinterpret_cast<float*>(smem16) + NW * 32 * LDO;
         constexpr int LPR = NB * 8;          // lanes per row (4 voxels each)
         constexpr int RPI = 32 / LPR;        // rows per half-wave per iteration
         constexpr int NIT = 16 / RPI;        // rows of a 32-row block this lane takes
@@ -913,7 +952,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
         if (A.residual) { if (A.stats) rows(T{}, T{}); else rows(T{}, F{}); }
         else { if (A.stats) rows(F{}, T{}); else rows(F{}, F{}); }
     } else {
-    if (A.stats) __syncthreads();                    // every wave is done with the activation tile
+    if (PAIR || A.stats) __syncthreads();            // every wave is done with the activation tile (pair form: the other quartet may be on the path above, with its barrier)
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
 #pragma unroll
@@ -944,11 +983,11 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     }
     if (A.stats) {
         __syncthreads();
-        if (tid < MB * 32 * 2) {
-            float t = red[tid];
+        if (qtid < MB * 32 * 2) {
+            float t = red[qtid];
 #pragma unroll
-            for (int w = 1; w < NW; ++w) t += red[w * MB * 64 + tid];      // fixed order
-            A.stats[((size_t)blockIdx.x * A.coutp + cout0) * 2 + tid] = t;
+            for (int w = 1; w < NW; ++w) t += red[w * MB * 64 + qtid];      // fixed order
+            A.stats[((size_t)blockIdx.x * A.coutp + cout0) * 2 + qtid] = t;
         }
         if (A.out_amax) {
 #pragma unroll
@@ -961,6 +1000,11 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
 template <int KS, int MB, int NB>
 __global__ __launch_bounds__(256, 2) void conv3d_f16x3_kernel(Conv16Args A) {
     conv3d_f16x3_body<KS, MB, NB>(A);
+}
+// Pair form: 8 waves over one tile and two 64-channel blocks (see the body); one workgroup per CU, the same 8 waves as two 4-wave ones
+template <int KS, int NB>
+__global__ __launch_bounds__(512, 1) void conv3d_f16x3_pair_kernel(Conv16Args A) {
+    conv3d_f16x3_body<KS, 2, NB, false, false, 0, true>(A);
 }
 // The same launch with a folded 1x1x1 skip convolution (SK): instantiations of their own, so that the skip loop's registers are
 // not charged to the kernels that never run it (the sub-pixel path got the same treatment).  conv_plan() can answer
@@ -1405,10 +1449,41 @@ static ConvKernel conv16_kernel(const ConvPlan& p, bool skip = false, int skip_c
     return nullptr;
 }
 
-static int launch(ConvKernel kern, const ConvPlan& p, const Conv16Args& a, hipStream_t st) {
+// The pair form of a planned launch (conv3d_f16x3_pair_kernel): the same plan -- tile, MB, NB, variant number, statistics layout
+// -- launched with 512 threads over (n_tiles, coutp / 128).  A pure function of the plan and of whether a folded skip rides
+// along: the plain f16x3 path, MB = 2, an even number of 64-channel blocks, and two tile buffers (or the eight waves' transposing
+// epilogue area and statistics partials) within the 160 KB of a CU, which excludes every stride-2 tile.  Unsplit NB = 4 launches
+// only: those are the classes that cleared the 2 % bar against their 4-wave form (profiles/conv_pair_pricing.txt: the 128^3
+// launches -9.8 % and -18.3 %; the split-K launches of the 32^3 and 16^3 levels -1.1 % .. +4.8 %, so they keep the 4-wave kernels,
+// and no launch of the networks reaches NB < 4 unsplit with 128 channels).  Returns the launch's dynamic LDS bytes, 0 = the launch
+// keeps the 4-wave kernel.
+#ifdef PIXIE_DIAG
+static int g_conv_keep_four_wave = 0;   // diagnostic switch (pixie_conv_kernel_variant with a null descriptor)
+#endif
+static size_t conv_pair_lds(const ConvPlan& p, bool skip) {
+#ifdef PIXIE_DIAG
+    if (g_conv_keep_four_wave) return 0;
+#endif
+    if (p.path != CONV_F16X3 || p.fullres || skip || p.MB != 2 || p.NB != 4 || p.slices != 1 || p.coutp % 128 != 0) return 0;
+    const size_t tiles = (size_t)2 * 4 * p.CS * sizeof(uint4);
+    const size_t red = (size_t)2 * 4 * p.MB * 32 * 2 * sizeof(float);
+    const size_t epi = p.epi_lds ? (size_t)8 * 32 * (p.NB * 32 + 4) * sizeof(float) + red : red;
+    const size_t lds = std::max(tiles, epi);
+    return lds <= 160 * 1024 ? lds : 0;
+}
+static ConvKernel conv16_pair_kernel(const ConvPlan& p) {
+#define PX_CONV16_PAIR(KS_, NB_) \
+    if (p.KS == KS_ && p.NB == NB_) return conv3d_f16x3_pair_kernel<KS_, NB_>;
+    PX_CONV16_PAIR(3, 4) PX_CONV16_PAIR(1, 4)
+#undef PX_CONV16_PAIR
+    return nullptr;
+}
+
+static int launch(ConvKernel kern, const ConvPlan& p, const Conv16Args& a, hipStream_t st, size_t pair_lds = 0) {
     PX_REQUIRE(kern != nullptr, "conv: no kernel variant for ksize=%d MB=%d NB=%d", p.KS, p.MB, p.NB);
     PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds_bytes, st, a);
+    if (pair_lds) hipLaunchKernelGGL(kern, dim3(p.grid.x, p.grid.y / 2, 1), dim3(512), pair_lds, st, a);
+    else hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds_bytes, st, a);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1458,7 +1533,8 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
     }
     PX_REQUIRE(p.refusal != CONV_BAD_LDS, "f16x3 conv: tile needs %zu B of LDS", p.lds_bytes);
     PX_REQUIRE(p.f16x3(), "f16x3 conv: bad sizes");
-    if (int rc = launch(conv16_kernel(p, a.sk_w16 != nullptr, a.sk_c0), p, a, st)) return rc;
+    const size_t pair_lds = conv_pair_lds(p, a.sk_w16 != nullptr);
+    if (int rc = launch(pair_lds ? conv16_pair_kernel(p) : conv16_kernel(p, a.sk_w16 != nullptr, a.sk_c0), p, a, st, pair_lds)) return rc;
     if (p.slices == 1) return 0;
     const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
     if (d->d_out_stats) {
@@ -1512,6 +1588,11 @@ extern "C" int64_t pixie_conv_workspace_bytes(const pixie_conv_desc* d) {
 // its own per-launch timings the way rocprofv3 groups them: by kernel name.)
 #ifdef PIXIE_DIAG
 extern "C" int pixie_conv_kernel_variant(const pixie_conv_desc* d, int* slices_out) {
+    if (!d) {   // the launcher-form switch: *slices_out = 1 keeps the 4-wave kernels, 0 gives the choice back to the plan
+        const int before = g_conv_keep_four_wave;
+        if (slices_out && (*slices_out == 0 || *slices_out == 1)) g_conv_keep_four_wave = *slices_out;
+        return before;
+    }
     const ConvPlan p = plan_of(d);
     if (slices_out) *slices_out = p.f16x3() ? p.slices : 1;
     if (!p.f16x3()) return 0;
@@ -1525,6 +1606,7 @@ extern "C" int pixie_conv_kernel_variant(const pixie_conv_desc* d, int* slices_o
 // without, the exact-fp32 launch of the same body.  Returns 1 (and leaves out alone) for descriptors that take neither.
 extern "C" int pixie_conv_tile_geometry(const pixie_conv_desc* d, int32_t out[10]) {
     const ConvPlan p = plan_of(d);
+    if (!out && d) return (int)conv_pair_lds(p, d->d_skip_w16 != nullptr);   // the launcher's form for this descriptor, as it is switched now
     if (!out || !p.tiled()) return 1;
     const int32_t v[10] = {p.TX, p.TY, p.TZ, p.tiles_x, p.tiles_y, p.tiles_z, p.epi_lds, p.slices, p.MB, p.NB};
     for (int i = 0; i < 10; ++i) out[i] = v[i];

@@ -776,6 +776,53 @@ int pixie_gs_densify_plan(const pixie_gs_densify_desc* desc, int64_t counts_out[
 int pixie_gs_densify_emit(const pixie_gs_densify_desc* desc, const pixie_gs_densify_outs* outs, void* stream);
 
 /* ======================================================================================
+ * (E) Occupancy mask -- the stage between the voxel files and the networks: pixie/voxel/voxelize.py:188-263
+ *     _create_occupancy_mask (and the same filters in compute_occupancy_point_cloud :331-400, with
+ *     f3rm_robot/optimize.py:44-89 remove_floating_clusters).  Open3D's remove_statistical_outlier and cluster_dbscan
+ *     are restated on the voxel lattice from their published algorithm.
+ * ====================================================================================== */
+typedef struct pixie_occupancy_desc {
+    const void* d_alphas;       /* (D, H, W) densities, float16 or float32 (a trailing axis of 1 is the same memory) */
+    const void* d_rgb;          /* (D, H, W, 3) colours, same dtype */
+    const float* d_axis_x; const float* d_axis_y; const float* d_axis_z;  /* voxel coordinates, D / H / W float32 each, as pixie_field_desc;
+                                   the three spacings must agree up to rounding (the reference: arange(min, max, voxel_size) per axis) */
+    double* d_stats;            /* NULL or device double[3]: cloud_mean, std, cloud_mean + std_ratio std of stage B */
+    int32_t dtype;              /* 0 = float16, 1 = float32 */
+    int32_t d, h, w;            /* the grid need not be cubic */
+    int32_t run_filters;        /* 0: stage A alone (voxelize.py:252-253) */
+    int32_t nb_neighbors;       /* stage B, >= 1 */
+    int32_t min_points;         /* stage C, >= 1 */
+    int32_t keep;               /* stage C: 0 = every voxel of a cluster (voxelize.py:250), 1 = the largest cluster, first maximum;
+                                   everything if there is no cluster (optimize.py:44-89) */
+    double voxel_size;          /* eps = voxel_size * eps_multiplier, the product taken in double */
+    double lattice_spacing;     /* spacing of the axes (need not equal voxel_size: compute_occupancy_point_cloud clusters a
+                                   linspace lattice with eps = 5 * 0.01); sizes the index neighbourhood that is searched, nothing else */
+    double alpha_threshold, gray_threshold;  /* rounded to float32 before the comparison, as torch compares a float32 tensor with a scalar */
+    double std_ratio;
+    double eps_multiplier;      /* > 0; eps / lattice_spacing < 30 */
+} pixie_occupancy_desc;
+/* Stage A: a voxel is a candidate iff float32(alpha) > alpha_threshold and ((r + g) + b) / 3 > gray_threshold in float32.
+ * Stage B (Open3D RemoveStatisticalOutliers): m_i = mean Euclidean distance of candidate i to its k' = min(nb_neighbors, M)
+ * nearest candidates, itself included at distance 0, in float64 on the float32 coordinates; the nearest are whole shells of
+ * integer squared offset, ties inside the last shell in a fixed order.  cloud_mean = sum m_i / M and std = sqrt(sum (m_i -
+ * cloud_mean)^2 / (M - 1)) by two fixed-order float64 reductions; voxel i survives iff m_i > 0 && m_i < cloud_mean + std_ratio std
+ * (M = 1 and M = 2 keep nothing; M = 0 gives an empty mask and is no error).
+ * Stage C (Open3D ClusterDBSCAN on the survivors): neighbours are the survivors with ((dx dx + dy dy) + dz dz) < eps eps in float64
+ * on differences of the float32 coordinates -- STRICT, unlike the closed ball of pixie_dbscan_roots; a voxel is core when its open
+ * ball holds >= min_points survivors, itself included; clusters are the components of the core voxels, numbered by ascending
+ * lowest core index in C order; a border voxel joins the lowest-numbered cluster with a core voxel in reach; the rest is noise.
+ * d_mask [D][H][W] receives 0 / 1.  d_mean_dist: NULL or [D][H][W] doubles, m_i for candidates and NaN elsewhere (not written when
+ * run_filters == 0, nor is d_stats).  d_counts: device int64[8] = candidates after the density threshold, after the gray
+ * threshold (M), after stage B, after stage C (= voxels set in d_mask), voxels that left stage B's fast path, number of clusters,
+ * two reserved zeros.  d_scratch: 16-byte aligned, pixie_occupancy_scratch_bytes(desc, with_mean_dist) bytes (-1 on a bad descriptor;
+ * only d, h, w are read); with_mean_dist != 0 says that the call will be given a d_mean_dist, which saves the 8 D H W bytes of the call's own.  Null pointers, nb_neighbors < 1, min_points < 1, eps_multiplier <= 0, a dimension < 1 and more than 2^31 voxels are
+ * refused before any launch.  No stream synchronise, no host read-back, no floating-point atomics: asynchronous on `stream` and
+ * bit-identical from run to run. */
+int64_t pixie_occupancy_scratch_bytes(const pixie_occupancy_desc* desc, int with_mean_dist);
+int pixie_occupancy_mask(const pixie_occupancy_desc* desc, uint8_t* d_mask, double* d_mean_dist, int64_t* d_counts, void* d_scratch,
+                         void* stream);
+
+/* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)
  * load; the production library libpixie_hip.so exports none of them and carries no trace buffer.

@@ -89,6 +89,17 @@ class FieldDesc(C.Structure):
                 ("nu_min", C.c_double), ("nu_max", C.c_double)]
 
 
+class OccupancyDesc(C.Structure):
+    """struct pixie_occupancy_desc"""
+    _fields_ = [("d_alphas", C.c_void_p), ("d_rgb", C.c_void_p),
+                ("d_axis_x", C.c_void_p), ("d_axis_y", C.c_void_p), ("d_axis_z", C.c_void_p), ("d_stats", C.c_void_p),
+                ("dtype", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("run_filters", C.c_int32), ("nb_neighbors", C.c_int32), ("min_points", C.c_int32), ("keep", C.c_int32),
+                ("voxel_size", C.c_double), ("lattice_spacing", C.c_double),
+                ("alpha_threshold", C.c_double), ("gray_threshold", C.c_double), ("std_ratio", C.c_double),
+                ("eps_multiplier", C.c_double)]
+
+
 class RasterDesc(C.Structure):
     """struct pixie_raster_desc"""
     _fields_ = [("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
@@ -267,6 +278,8 @@ SIGNATURES = {
     "pixie_gs_densify_workspace_bytes": (_I64, [_I64]),
     "pixie_gs_densify_plan": (_I, [C.POINTER(GsDensifyDesc), C.POINTER(_I64), C.POINTER(_I64), _VP]),
     "pixie_gs_densify_emit": (_I, [C.POINTER(GsDensifyDesc), C.POINTER(GsDensifyOuts), _VP]),
+    "pixie_occupancy_scratch_bytes": (_I64, [C.POINTER(OccupancyDesc), _I]),
+    "pixie_occupancy_mask": (_I, [C.POINTER(OccupancyDesc), _VP, _VP, _VP, _VP, _VP]),
 }
 
 # entry points that exist only in the PIXIE_DIAG build (include/pixie_hip.h, last section)

@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpixie_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpixie_hip_diag.so")   # same sources + -DPIXIE_DIAG (tests, profilers)
 ARCH = "gfx950"
-SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip"]
+SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip", "occupancy.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
 # Per-file flags.  mpm.hip: hipcc's SLP vectoriser turns a third of the fused MPM kernel's fp32 arithmetic into packed
@@ -37,8 +37,11 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 # knn.hip: the same, for knn_math.h and tests/test_knn_math.py: distCUDA2 is bit-equal to a float32 brute force in the same order.
 # gs_optim.hip: the same, for gs_optim_math.h: the Adam update rounds in the order torch's kernels do; it moves 28 bytes per
 # element, so the unfused arithmetic is not what bounds it.
+# occupancy.hip: the same, for occupancy_math.h and tests/test_occupancy_math.py: the eps-ball test of the cluster filter is the
+# float64 expression ((dx dx + dy dy) + dz dz) < eps eps as written, which decides lattice pairs at exactly eps by its rounding.
 EXTRA_FLAGS = {"mpm.hip": ["-fno-slp-vectorize"], "raster.hip": ["-ffp-contract=off"], "raster_backward.hip": ["-ffp-contract=off"],
-               "scene_ingest.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "gs_optim.hip": ["-ffp-contract=off"]}
+               "scene_ingest.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "gs_optim.hip": ["-ffp-contract=off"],
+               "occupancy.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -823,6 +823,43 @@ int pixie_occupancy_mask(const pixie_occupancy_desc* desc, uint8_t* d_mask, doub
                          void* stream);
 
 /* ======================================================================================
+ * (F) Language-query part segmentation -- material_mode=vlm, pixie/voxel/segmentation.py: run_clip and
+ *     clip_part_segmentation (:98-168), local_post_process_segmentation (:190-226, sklearn KDTree + scipy.stats.mode in
+ *     a Python loop) and the material grid of save_segmented_point_cloud (:429-452).
+ * ====================================================================================== */
+#define PIXIE_PART_SEG_COUNTS 40
+typedef struct pixie_part_seg_desc {
+    const void* d_features;     /* (D, H, W, C) float16, the layout voxelize.py writes; 16-byte aligned */
+    const uint8_t* d_mask;      /* (D, H, W), != 0 = a masked voxel */
+    const float* d_queries;     /* (K, C) float32 text embeddings, not normalised */
+    const float* d_props;       /* NULL or (K, 4) float32: density, E, nu, material_id per part */
+    int32_t d, h, w;            /* the grid need not be cubic */
+    int32_t channels;           /* C: a multiple of 8, <= 2048 */
+    int32_t n_parts;            /* K: 1 .. 32, and K C 4 <= 96 KB (the queries are staged in LDS) */
+    int32_t vote_k;             /* 0: no vote; 1 .. 255: neighbours of the k-nearest-neighbour vote */
+    float temperature;          /* softmax temperature T > 0 (the reference: 0.1) */
+    float background_id;        /* material id of the rows outside the mask (the reference: 7) */
+} pixie_part_seg_desc;
+/* Stage A, every masked voxel: sim_j = <f, q_j> / (|f| |q_j|) in float32 on the widened row, d_labels = argmax_j sim_j (first
+ * maximum), d_scores = 1 / sum_j exp((sim_j - sim_max) / T), i.e. softmax(sim / T)[label]; a row of zero norm gets label 0 and
+ * score NaN.  Outside the mask d_labels = -1 and d_scores = NaN.  d_counts: device int64[PIXIE_PART_SEG_COUNTS] = voxels per part
+ * (stage A labels, 32 slots), masked voxels, voxels that left the vote's fast path, reserved zeros.
+ * Stage B (vote_k > 0), every masked voxel: d_voted [D][H][W] = the most frequent stage-A label among its k' = min(vote_k, masked
+ * voxels) nearest masked voxels, itself included, neighbours ordered by (integer squared index offset, C-order index), equal
+ * counts to the smallest label; -1 outside the mask.  d_voted must be NULL iff vote_k == 0.
+ * d_material (iff d_props): [D][H][W][4] float32, d_props[label] (the voted label if stage B ran) on the mask and
+ * [0, 0, 0, background_id] elsewhere; 16-byte aligned.
+ * d_scratch: 16-byte aligned, pixie_part_seg_scratch_bytes(desc) bytes (-1 on a bad descriptor; the pointers are not read).
+ * Shapes outside the limits above are refused before any launch.  No stream synchronise, no host read-back, no floating-point
+ * atomics: asynchronous on `stream` and bit-identical from run to run. */
+int64_t pixie_part_seg_scratch_bytes(const pixie_part_seg_desc* desc);
+int pixie_part_segmentation(const pixie_part_seg_desc* desc, int8_t* d_labels, float* d_scores, int8_t* d_voted, float* d_material,
+                            int64_t* d_counts, void* d_scratch, void* stream);
+/* The material fill alone, for labels that exist already: labels outside [0, n_parts) give the background row. */
+int pixie_part_material_grid(const int8_t* d_labels, const float* d_props, int n_parts, int64_t n_voxels, float background_id,
+                             float* d_material, void* stream);
+
+/* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)
  * load; the production library libpixie_hip.so exports none of them and carries no trace buffer.

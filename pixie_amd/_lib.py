@@ -100,6 +100,16 @@ class OccupancyDesc(C.Structure):
                 ("eps_multiplier", C.c_double)]
 
 
+PART_SEG_COUNTS = 40   # PIXIE_PART_SEG_COUNTS
+
+
+class PartSegDesc(C.Structure):
+    """struct pixie_part_seg_desc"""
+    _fields_ = [("d_features", C.c_void_p), ("d_mask", C.c_void_p), ("d_queries", C.c_void_p), ("d_props", C.c_void_p),
+                ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("n_parts", C.c_int32),
+                ("vote_k", C.c_int32), ("temperature", C.c_float), ("background_id", C.c_float)]
+
+
 class RasterDesc(C.Structure):
     """struct pixie_raster_desc"""
     _fields_ = [("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
@@ -280,6 +290,9 @@ SIGNATURES = {
     "pixie_gs_densify_emit": (_I, [C.POINTER(GsDensifyDesc), C.POINTER(GsDensifyOuts), _VP]),
     "pixie_occupancy_scratch_bytes": (_I64, [C.POINTER(OccupancyDesc), _I]),
     "pixie_occupancy_mask": (_I, [C.POINTER(OccupancyDesc), _VP, _VP, _VP, _VP, _VP]),
+    "pixie_part_seg_scratch_bytes": (_I64, [C.POINTER(PartSegDesc)]),
+    "pixie_part_segmentation": (_I, [C.POINTER(PartSegDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pixie_part_material_grid": (_I, [_VP, _VP, _I, _I64, C.c_float, _VP, _VP]),
 }
 
 # entry points that exist only in the PIXIE_DIAG build (include/pixie_hip.h, last section)

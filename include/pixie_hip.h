@@ -860,6 +860,78 @@ int pixie_part_material_grid(const int8_t* d_labels, const float* d_props, int n
                              float* d_material, void* stream);
 
 /* ======================================================================================
+ * (G) NeRF feature-field query -- pixie/voxel/voxelize.py: extract_clip_voxel_grid (:17-141) through
+ *     f3rm_robot/field_adapter.py (:28-72): multiresolution hash grids (+ frequency block, + extra input columns) feeding
+ *     64-wide ReLU MLPs, the networks the reference evaluates with tiny-cuda-nn.
+ * ====================================================================================== */
+#define PIXIE_HASHMLP_MAX_LEVELS 16
+#define PIXIE_HASHMLP_MAX_LAYERS 5      /* up to 4 hidden layers + the output layer */
+#define PIXIE_HASHMLP_MAX_INPUT 160     /* widest input row: levels * features + 6 * frequencies + extra columns */
+#define PIXIE_HASHMLP_MAX_OUTPUT 1024
+/* One level of a grid.  For a unit-cube position p: q = p * scale + shift (float32, unfused), c0 = floor(q), w = q - c0, corners
+ * c0 + {0,1}^3 with trilinear weights from w; corner (x, y, z) reads table row
+ *   (dense ? x + y res + z res^2 : x ^ y 2654435761 ^ z 805459861) [uint32] % size + offset. */
+typedef struct pixie_hashgrid_level {
+    float scale, shift;
+    uint32_t res, size, offset, dense;
+} pixie_hashgrid_level;
+typedef struct pixie_hashmlp_desc {
+    int32_t n_levels;              /* 0 .. 16 (0: the input row is the extra columns alone) */
+    int32_t features_per_level;    /* 2, 4 or 8 */
+    int32_t n_frequencies;         /* 0 = no frequency block, else 1 .. 8: 6 n columns after the grid columns, tiny-cuda-nn's order:
+                                    * column j has dim j / (2 n), octave (j / 2) % n, value sin(2^octave pi x + (j % 2) pi / 2) */
+    int32_t n_extra;               /* float32 input columns appended last, read from d_extra */
+    int32_t n_hidden;              /* 1 .. 4 hidden layers, each 64 wide, ReLU */
+    int32_t out_dim;               /* 1 .. 1024 */
+    int32_t out_activation;        /* 0 none, 1 sigmoid, 2 exp */
+    int32_t pad_;
+    pixie_hashgrid_level level[PIXIE_HASHMLP_MAX_LEVELS];
+    const float* d_table;          /* (table_rows, features_per_level) float32, 16-byte aligned */
+    int64_t table_rows;            /* every level's offset + size <= table_rows */
+    const float* d_weight[PIXIE_HASHMLP_MAX_LAYERS];   /* layer i of n_hidden + 1: (out_i, in_i) row-major float32 */
+    const float* d_bias[PIXIE_HASHMLP_MAX_LAYERS];     /* NULL (no bias) or (out_i) float32 */
+} pixie_hashmlp_desc;
+/* d_out (n, out_dim) float32 = act(MLP(row)) with row = [grid columns | frequency columns | d_extra (n, n_extra)] of the unit-cube
+ * positions d_positions (n, 3) float32 (NULL allowed iff n_levels == 0 and n_frequencies == 0; d_extra NULL iff n_extra == 0).
+ * float32 throughout, the layers on the float32 matrix instructions; the input row and the hidden activations stay on chip.
+ * Anything outside the limits above (or an input row wider than PIXIE_HASHMLP_MAX_INPUT) is refused before any launch.
+ * Asynchronous on `stream`, bit-identical from run to run. */
+int pixie_hashmlp_forward(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, float* d_out,
+                          void* stream);
+
+typedef struct pixie_field_voxelize_desc {
+    pixie_hashmlp_desc density;    /* out_dim = 1 + G <= 63, out_activation 0: column 0 the log density, columns 1.. the geometry
+                                    * features (nerfacto_field.py:203-232) */
+    pixie_hashmlp_desc color;      /* n_levels 0, n_frequencies 0, n_extra = G, out_dim 3, sigmoid: the colour head with the constant
+                                    * direction and appearance inputs folded into its first bias by the caller */
+    pixie_hashmlp_desc feature;    /* out_dim C, out_activation 0 (f3rm/feature_field.py:94-113) */
+    const float* d_axis_x;         /* all three NULL, or the voxel coordinates themselves: (D), (H), (W) float32 device arrays.  The */
+    const float* d_axis_y;         /* reference's lattice is torch.arange(min, max, voxel_size) evaluated on the CPU, whose vectorised */
+    const float* d_axis_z;         /* loop rounds differently from the formula below (and with the CPU's vector width) */
+    double min_bounds[3];          /* without axes voxel (i, j, k) sits at float32(min_bounds + (i, j, k) * voxel_size) computed in double */
+    double voxel_size;             /* also the delta of alpha = 1 - exp(-density * float32(voxel_size)) */
+    int32_t d, h, w;
+    int32_t contraction;           /* 1: L-infinity scene contraction, then (p + 2) / 4;  0: (p - aabb_lo) / (aabb_hi - aabb_lo) */
+    int32_t alpha_weighted;        /* 1: features are multiplied by the float32 alpha before rounding to float16 */
+    float average_init_density;
+    float world_to_nerf[12];       /* 3 x 4 row-major: n_r = ((A[r][0] x + A[r][1] y) + A[r][2] z) + A[r][3] */
+    float aabb[6];                 /* lo[3], hi[3]; read when contraction == 0 */
+} pixie_field_voxelize_desc;
+/* d_features (D, H, W, C) float16, d_alpha (D, H, W, 1) float16, d_rgb (D, H, W, 3) float16, d_density NULL or (D, H, W) float32;
+ * d_scratch (D, H, W) float32, which holds the float32 alpha afterwards.  The density net sees p * selector, selector = all of
+ * 0 < p < 1, and density = average_init_density * exp(h_0) * selector; the feature net sees p itself.  Every float16 output is the
+ * float32 value rounded to nearest even.  Two launches, no stream synchronise, no host read-back, no floating-point atomics:
+ * asynchronous on `stream` and bit-identical from run to run. */
+int pixie_field_voxelize(const pixie_field_voxelize_desc* vdesc, void* d_features, void* d_alpha, void* d_rgb, float* d_density,
+                         float* d_scratch, void* stream);
+/* The same kernels on n world points d_world (n, 3) float32 in place of the lattice (min_bounds, voxel_size, d, h, w and
+ * alpha_weighted are not read), with float32 outputs, FeatureFieldAdapter's surface: d_features (n, C) the raw feature net output,
+ * d_alpha (n) = 1 - exp(-density * float32(delta)), d_rgb (n, 3), d_density (n).  Any output may be NULL and is then not computed.
+ * A point gets the bits the lattice call gives a voxel at the same float32 position, before the rounding to float16. */
+int pixie_field_query_points(const pixie_field_voxelize_desc* vdesc, const float* d_world, int64_t n, double delta, float* d_features,
+                             float* d_alpha, float* d_rgb, float* d_density, void* stream);
+
+/* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)
  * load; the production library libpixie_hip.so exports none of them and carries no trace buffer.

@@ -110,6 +110,33 @@ class PartSegDesc(C.Structure):
                 ("vote_k", C.c_int32), ("temperature", C.c_float), ("background_id", C.c_float)]
 
 
+HASHMLP_MAX_LEVELS, HASHMLP_MAX_LAYERS, HASHMLP_MAX_INPUT, HASHMLP_MAX_OUTPUT = 16, 5, 160, 1024   # PIXIE_HASHMLP_*
+
+
+class HashGridLevel(C.Structure):
+    """struct pixie_hashgrid_level"""
+    _fields_ = [("scale", C.c_float), ("shift", C.c_float), ("res", C.c_uint32), ("size", C.c_uint32), ("offset", C.c_uint32),
+                ("dense", C.c_uint32)]
+
+
+class HashMlpDesc(C.Structure):
+    """struct pixie_hashmlp_desc"""
+    _fields_ = [("n_levels", C.c_int32), ("features_per_level", C.c_int32), ("n_frequencies", C.c_int32), ("n_extra", C.c_int32),
+                ("n_hidden", C.c_int32), ("out_dim", C.c_int32), ("out_activation", C.c_int32), ("pad_", C.c_int32),
+                ("level", HashGridLevel * HASHMLP_MAX_LEVELS),
+                ("d_table", C.c_void_p), ("table_rows", C.c_int64),
+                ("d_weight", C.c_void_p * HASHMLP_MAX_LAYERS), ("d_bias", C.c_void_p * HASHMLP_MAX_LAYERS)]
+
+
+class FieldVoxelizeDesc(C.Structure):
+    """struct pixie_field_voxelize_desc"""
+    _fields_ = [("density", HashMlpDesc), ("color", HashMlpDesc), ("feature", HashMlpDesc),
+                ("d_axis_x", C.c_void_p), ("d_axis_y", C.c_void_p), ("d_axis_z", C.c_void_p),
+                ("min_bounds", C.c_double * 3), ("voxel_size", C.c_double),
+                ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("contraction", C.c_int32), ("alpha_weighted", C.c_int32),
+                ("average_init_density", C.c_float), ("world_to_nerf", C.c_float * 12), ("aabb", C.c_float * 6)]
+
+
 class RasterDesc(C.Structure):
     """struct pixie_raster_desc"""
     _fields_ = [("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
@@ -293,6 +320,9 @@ SIGNATURES = {
     "pixie_part_seg_scratch_bytes": (_I64, [C.POINTER(PartSegDesc)]),
     "pixie_part_segmentation": (_I, [C.POINTER(PartSegDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pixie_part_material_grid": (_I, [_VP, _VP, _I, _I64, C.c_float, _VP, _VP]),
+    "pixie_hashmlp_forward": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP]),
+    "pixie_field_voxelize": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pixie_field_query_points": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _I64, _D, _VP, _VP, _VP, _VP, _VP]),
 }
 
 # entry points that exist only in the PIXIE_DIAG build (include/pixie_hip.h, last section)

@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpixie_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpixie_hip_diag.so")   # same sources + -DPIXIE_DIAG (tests, profilers)
 ARCH = "gfx950"
-SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip", "occupancy.hip", "part_segmentation.hip"]
+SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip", "occupancy.hip", "part_segmentation.hip", "field_query.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
 # Per-file flags.  mpm.hip: hipcc's SLP vectoriser turns a third of the fused MPM kernel's fp32 arithmetic into packed
@@ -42,9 +42,12 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 # part_segmentation.hip: the same, for part_seg_math.h and tests/test_part_seg_math.py: a lane's share of a dot product is the
 # float32 chain acc = acc + f q as written, so the host build of the header carries the device's bits up to expf; the kernel moves
 # 2 C bytes per masked voxel against 2 K C flops, so the unfused arithmetic is not what bounds it.
+# field_query.hip: the same, for hashgrid_math.h and tests/test_hashgrid_math.py: lattice coordinate, affine, contraction, selector and
+# the scaled position of every level round as a float32 NumPy evaluation does, so cells and selectors are equal; the layers run on
+# matrix instructions, which fuse regardless.
 EXTRA_FLAGS = {"mpm.hip": ["-fno-slp-vectorize"], "raster.hip": ["-ffp-contract=off"], "raster_backward.hip": ["-ffp-contract=off"],
                "scene_ingest.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "gs_optim.hip": ["-ffp-contract=off"],
-               "occupancy.hip": ["-ffp-contract=off"], "part_segmentation.hip": ["-ffp-contract=off"]}
+               "occupancy.hip": ["-ffp-contract=off"], "part_segmentation.hip": ["-ffp-contract=off"], "field_query.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

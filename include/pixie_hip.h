@@ -899,6 +899,32 @@ typedef struct pixie_hashmlp_desc {
 int pixie_hashmlp_forward(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, float* d_out,
                           void* stream);
 
+/* ---- training: the same network with gradients (pixie_amd/csrc/field_query_backward.hip) ----
+ * pixie_hashmlp_forward_saved is pixie_hashmlp_forward (the same bits in d_out) and also fills d_saved with what the backward reads,
+ * channel-major float32: the input row [in_dim][n], then the post-ReLU activations of hidden layer k as [64][n], k = 0.. n_hidden - 1:
+ *     saved_bytes = 4 n (in_dim + 64 n_hidden),  in_dim = n_levels features_per_level + 6 n_frequencies + n_extra.
+ * pixie_hashmlp_backward takes the forward's inputs, its d_out, d_saved and d_dout = dL/d_out (n, out_dim) and WRITES (does not
+ * accumulate) every gradient whose pointer is not NULL.  Positions get no gradient.  d_scratch, 256-byte aligned, of scratch_bytes:
+ *     [0, 256)     header: uint32 bits of M = max |dX_grid|, int32 shift s the call used, int32 state (0 scattered, 1 M == 0, 2 M not finite)
+ *     then, each rounded up to 256 bytes: dZ of the hidden layers 4 (64 n_hidden n) | dX of the grid columns 4 (n_levels F n) |
+ *     weight-gradient slab partials 4 max_layers(slabs (out in + out)) | the table's accumulators 8 table_rows F,
+ *     slabs(layer) = clamp(1024 / (ceil(out / 64) ceil(in / 64)), 1, min(ceil(n / 64), 256)).
+ * The table gradient is a 64-bit fixed-point integer scatter (csrc/hashgrid_grad_math.h): bit-identical from run to run and under any
+ * permutation of the points; weight and bias gradients sum fixed slabs of points in slab order: bit-identical from run to run.
+ * M == 0 gives a zero table gradient; M not finite (an Inf or NaN in d_dout) fills the WHOLE table gradient with NaN.
+ * Refusals are the forward's, and n > 2^24.  Asynchronous on `stream`: no synchronise, no host read-back. */
+typedef struct pixie_hashmlp_grads {      /* any pointer may be NULL: that gradient is not computed */
+    float* d_table;                        /* (table_rows, F) */
+    float* d_weight[PIXIE_HASHMLP_MAX_LAYERS];
+    float* d_bias[PIXIE_HASHMLP_MAX_LAYERS];
+    float* d_extra;                        /* (n, n_extra) */
+} pixie_hashmlp_grads;
+int pixie_hashmlp_train_bytes(const pixie_hashmlp_desc* desc, int64_t n, int64_t* saved_bytes, int64_t* scratch_bytes);
+int pixie_hashmlp_forward_saved(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, float* d_out,
+                                void* d_saved, void* stream);
+int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, const float* d_out,
+                           const void* d_saved, const float* d_dout, const pixie_hashmlp_grads* grads, void* d_scratch, void* stream);
+
 typedef struct pixie_field_voxelize_desc {
     pixie_hashmlp_desc density;    /* out_dim = 1 + G <= 63, out_activation 0: column 0 the log density, columns 1.. the geometry
                                     * features (nerfacto_field.py:203-232) */

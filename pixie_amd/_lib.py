@@ -128,6 +128,12 @@ class HashMlpDesc(C.Structure):
                 ("d_weight", C.c_void_p * HASHMLP_MAX_LAYERS), ("d_bias", C.c_void_p * HASHMLP_MAX_LAYERS)]
 
 
+class HashMlpGrads(C.Structure):
+    """struct pixie_hashmlp_grads"""
+    _fields_ = [("d_table", C.c_void_p), ("d_weight", C.c_void_p * HASHMLP_MAX_LAYERS), ("d_bias", C.c_void_p * HASHMLP_MAX_LAYERS),
+                ("d_extra", C.c_void_p)]
+
+
 class FieldVoxelizeDesc(C.Structure):
     """struct pixie_field_voxelize_desc"""
     _fields_ = [("density", HashMlpDesc), ("color", HashMlpDesc), ("feature", HashMlpDesc),
@@ -321,6 +327,9 @@ SIGNATURES = {
     "pixie_part_segmentation": (_I, [C.POINTER(PartSegDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pixie_part_material_grid": (_I, [_VP, _VP, _I, _I64, C.c_float, _VP, _VP]),
     "pixie_hashmlp_forward": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP]),
+    "pixie_hashmlp_train_bytes": (_I, [C.POINTER(HashMlpDesc), _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "pixie_hashmlp_forward_saved": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP]),
+    "pixie_hashmlp_backward": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP, C.POINTER(HashMlpGrads), _VP, _VP]),
     "pixie_field_voxelize": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pixie_field_query_points": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _I64, _D, _VP, _VP, _VP, _VP, _VP]),
 }

@@ -957,6 +957,72 @@ int pixie_field_voxelize(const pixie_field_voxelize_desc* vdesc, void* d_feature
 int pixie_field_query_points(const pixie_field_voxelize_desc* vdesc, const float* d_world, int64_t n, double delta, float* d_features,
                              float* d_alpha, float* d_rgb, float* d_density, void* stream);
 
+/* ---- differentiable ray compositing (pixie_amd/csrc/ray_render.hip) ----
+ * What lies between a NeRF's per-sample outputs and its loss: RaySamples.get_weights, RGBRenderer.combine_rgb, AccumulationRenderer,
+ * DepthRenderer (median and expected) and f3rm's FeatureRenderer, for unpacked samples, forward and backward.  All arrays are
+ * float32, contiguous, on the device; R = n_rays, S = n_samples, C = n_channels.
+ *     x_i = delta_i density_i,  w_i = nan_to_num((1 - exp(-x_i)) exp(-sum_{j<i} x_j)),  A = sum w_i,  m_i = (start_i + end_i) / 2
+ *     rgb = sum w_i rgb_i + bg (1 - A),  expected depth = sum w_i m_i / (A + 1e-10) (NOT clipped: the clip is global over the batch
+ *     and the caller's),  median depth = m_j for the first j whose running sum of w reaches 0.5 (S - 1 if none),  feature_c = sum w_i f_ic
+ * Two modes.  Densities given (d_densities and d_deltas set, inputs.d_weights NULL in the forward): the weights are computed and
+ * written to outputs.d_weights, which is required.  Weights given (d_densities NULL, inputs.d_weights set): the renderers alone;
+ * outputs.d_weights must be NULL.  Any other output pointer may be NULL and is then not computed; an output needs its inputs
+ * (depths: starts and ends; rgb: d_rgb; feature: d_features).
+ * Limits: 1 <= R <= 2^24, 1 <= S <= 1024, C a multiple of 4 in [0, 2048], S <= 256 when C > 0; feature arrays 16-byte aligned.
+ * Anything else is refused with a non-zero return before any launch.  Every sum has one fixed order: bit-identical from run to run,
+ * under a permutation of the rays and for any R.  No floating-point atomics.  Asynchronous on `stream`: no synchronise, no host
+ * read-back. */
+typedef struct pixie_ray_desc {
+    int64_t n_rays;
+    int32_t n_samples;
+    int32_t n_channels;            /* 0: no features */
+    int32_t background;            /* 0 none ("random": nothing is added), 1 the constant bg, 2 the ray's last sample's rgb */
+    float bg[3];
+} pixie_ray_desc;
+typedef struct pixie_ray_inputs {
+    const float* d_densities;      /* (R, S) or NULL */
+    const float* d_deltas;         /* (R, S), with d_densities */
+    const float* d_weights;        /* (R, S): the given weights; in the backward of the density mode, the forward's outputs.d_weights */
+    const float* d_starts;         /* (R, S) or NULL, with d_ends */
+    const float* d_ends;
+    const float* d_rgb;            /* (R, S, 3) or NULL */
+    const float* d_features;       /* (R, S, C) or NULL */
+} pixie_ray_inputs;
+typedef struct pixie_ray_outputs {
+    float* d_weights;              /* (R, S) */
+    float* d_accumulation;         /* (R) */
+    float* d_expected_depth;       /* (R) */
+    float* d_median_depth;         /* (R) */
+    float* d_rgb;                  /* (R, 3) */
+    float* d_feature;              /* (R, C) */
+} pixie_ray_outputs;
+/* dL/d(output), same shapes; NULL = that output has no gradient.  The median depth has none. */
+typedef struct pixie_ray_upstream {
+    const float* d_weights;        /* density mode only: the weights are an output there */
+    const float* d_accumulation;
+    const float* d_expected_depth;
+    const float* d_rgb;
+    const float* d_feature;
+} pixie_ray_upstream;
+/* gradients, WRITTEN (not accumulated); NULL = not wanted.  Deltas, starts and ends get none. */
+typedef struct pixie_ray_grads {
+    float* d_densities;            /* (R, S) density mode */
+    float* d_weights;              /* (R, S) weights mode */
+    float* d_rgb;                  /* (R, S, 3); needs upstream.d_rgb */
+    float* d_features;             /* (R, S, C); needs upstream.d_feature */
+} pixie_ray_grads;
+/* The backward forms g_i = dL/dw_i as the sum, in this order, of the terms of the weights output, the feature (its partial dot
+ * products per 256-channel chunk, in chunk order), the accumulation, the expected depth and the rgb, each term one float32; in the
+ * weights mode that is d_weights.  In the density mode g_i is zeroed where nan_to_num replaced the weight, and
+ *     d_density_k = delta_k (g_k exp(-x_k) exp(-P_k) - sum_{i>k} g_i w_i),
+ * finite wherever the upstream gradients are: a NaN density gives zeros from its sample onward, not NaN.
+ * d_scratch: scratch_bytes = 4 R ceil(C / 256) S, read and written only when upstream.d_feature is set and d_densities or d_weights
+ * is wanted; may be NULL otherwise. */
+int pixie_ray_composite_bytes(const pixie_ray_desc* desc, int64_t* scratch_bytes);
+int pixie_ray_composite_forward(const pixie_ray_desc* desc, const pixie_ray_inputs* inputs, const pixie_ray_outputs* outputs, void* stream);
+int pixie_ray_composite_backward(const pixie_ray_desc* desc, const pixie_ray_inputs* inputs, const pixie_ray_upstream* upstream,
+                                 const pixie_ray_grads* grads, void* d_scratch, void* stream);
+
 /* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)

@@ -134,6 +134,37 @@ class HashMlpGrads(C.Structure):
                 ("d_extra", C.c_void_p)]
 
 
+RAY_MAX_SAMPLES, RAY_MAX_FEATURE_SAMPLES, RAY_MAX_CHANNELS, RAY_MAX_RAYS = 1024, 256, 2048, 1 << 24   # csrc/ray_render_math.h
+
+
+class RayDesc(C.Structure):
+    """struct pixie_ray_desc"""
+    _fields_ = [("n_rays", C.c_int64), ("n_samples", C.c_int32), ("n_channels", C.c_int32), ("background", C.c_int32), ("bg", C.c_float * 3)]
+
+
+class RayInputs(C.Structure):
+    """struct pixie_ray_inputs"""
+    _fields_ = [("d_densities", C.c_void_p), ("d_deltas", C.c_void_p), ("d_weights", C.c_void_p), ("d_starts", C.c_void_p),
+                ("d_ends", C.c_void_p), ("d_rgb", C.c_void_p), ("d_features", C.c_void_p)]
+
+
+class RayOutputs(C.Structure):
+    """struct pixie_ray_outputs"""
+    _fields_ = [("d_weights", C.c_void_p), ("d_accumulation", C.c_void_p), ("d_expected_depth", C.c_void_p), ("d_median_depth", C.c_void_p),
+                ("d_rgb", C.c_void_p), ("d_feature", C.c_void_p)]
+
+
+class RayUpstream(C.Structure):
+    """struct pixie_ray_upstream"""
+    _fields_ = [("d_weights", C.c_void_p), ("d_accumulation", C.c_void_p), ("d_expected_depth", C.c_void_p), ("d_rgb", C.c_void_p),
+                ("d_feature", C.c_void_p)]
+
+
+class RayGrads(C.Structure):
+    """struct pixie_ray_grads"""
+    _fields_ = [("d_densities", C.c_void_p), ("d_weights", C.c_void_p), ("d_rgb", C.c_void_p), ("d_features", C.c_void_p)]
+
+
 class FieldVoxelizeDesc(C.Structure):
     """struct pixie_field_voxelize_desc"""
     _fields_ = [("density", HashMlpDesc), ("color", HashMlpDesc), ("feature", HashMlpDesc),
@@ -330,6 +361,9 @@ SIGNATURES = {
     "pixie_hashmlp_train_bytes": (_I, [C.POINTER(HashMlpDesc), _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "pixie_hashmlp_forward_saved": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP]),
     "pixie_hashmlp_backward": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP, C.POINTER(HashMlpGrads), _VP, _VP]),
+    "pixie_ray_composite_bytes": (_I, [C.POINTER(RayDesc), C.POINTER(_I64)]),
+    "pixie_ray_composite_forward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayOutputs), _VP]),
+    "pixie_ray_composite_backward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayUpstream), C.POINTER(RayGrads), _VP, _VP]),
     "pixie_field_voxelize": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pixie_field_query_points": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _I64, _D, _VP, _VP, _VP, _VP, _VP]),
 }

@@ -4,7 +4,7 @@ The reference trains its field with `ns-train f3rm` (pipeline.py:84-132); all th
 tcnn.NetworkWithInputEncoding / FullyFusedMLP modules (nerfacto_field.py, f3rm/feature_field.py:71-82), which exist for CUDA only.
 What they give FeatureFieldModel.get_outputs / get_loss_dict is a module that maps positions to outputs with gradients for the hash
 table and the MLP weights under torch.autograd.  This file is that module over pixie_amd/csrc/field_query_backward.hip; everything above it
-(ray sampling, get_weights, the renderers, the losses, torch.optim.Adam) is plain torch.
+(ray sampling, the losses, torch.optim.Adam) is plain torch, except get_weights and the renderers: pixie_amd/ray_render.py.
 
     TrainableHashMLP(levels, table, weights, biases, ...)    torch.nn.Module; parameters table, weights, biases; forward(positions, extra)
     TrainableHashMLP.from_hashmlp(h) / .to_hashmlp()         both ways over the same storage

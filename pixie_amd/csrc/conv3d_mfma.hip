@@ -23,6 +23,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "conv_launch.h"
 #include "conv_plan.h"
 
 namespace pixie {
@@ -225,7 +226,7 @@ static int launch_variant(const ConvArgs& a, size_t lds_bytes, dim3 grid, hipStr
 
 using namespace pixie;
 
-extern "C" int pixie_conv_cout_padded(int c_out) { return (c_out + 31) / 32 * 32; }
+extern "C" int pixie_conv_cout_padded(int c_out) { return conv_cout_padded(c_out); }
 
 extern "C" int pixie_conv_pack_weights(const float* d_w, float* d_packed, int c_out, int c_in, int ksize, void* stream) {
     PX_REQUIRE(d_w && d_packed && c_out > 0 && c_in > 0 && (ksize == 1 || ksize == 3), "pixie_conv_pack_weights: bad arguments");

@@ -29,6 +29,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "conv_launch.h"
 #include "conv_plan.h"
 
 namespace pixie {
@@ -524,7 +525,7 @@ struct Exec {
         if (b.cin != b.cout) {
             if (net->fold_skip && skip_foldable(h, b.cout, 3, parts)) {
                 // out = conv(h) + skip_connection(x) in ONE launch: the 1x1x1 convolution rides in the accumulators of the second
-                // 3^3 convolution, the skip tensor never exists (conv3d_f16x3.hip, "folded skip")
+                // 3^3 convolution, the skip tensor never exists (conv16_skip.h, "folded skip")
                 skip.reset();
                 for (auto& t : parts) stats(t);
                 o2.skip_parts = &parts; o2.skip_key = p + ".skip_connection";

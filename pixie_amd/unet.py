@@ -471,7 +471,7 @@ class UNetRunner:
             if (self.fold_skip and self._f16x3 and ops.f16x3_ok([h], 1) and ops.f16x3_ok(parts, 1)
                     and ops.skip_foldable(h, b.cout, 3, parts)):
                 # out = conv(h) + skip_connection(x) in ONE launch: the 1x1x1 convolution rides in the accumulators of the
-                # second 3^3 convolution, the skip tensor never exists (csrc/conv3d_f16x3.hip, "folded skip")
+                # second 3^3 convolution, the skip tensor never exists (csrc/conv16_skip.h, "folded skip")
                 skip = None
                 fold = dict(parts=parts, w16=self._w16(p + ".skip_connection"), bias=self._b(p + ".skip_connection"),
                             amax=[self._amax(cache, t) for t in parts])

@@ -80,7 +80,7 @@ class TorchRefOps:
 
 
 def _scale_exponent(bound: float) -> int:
-    """Mirror of scale_exponent() in pixie_amd/csrc/conv3d_f16x3.hip."""
+    """Mirror of scale_exponent() in pixie_amd/csrc/conv16_device.h."""
     import math
     if not (bound > 0.0) or math.isinf(bound) or math.isnan(bound):
         return 0

@@ -48,7 +48,7 @@ CASES = [
 
 def staged_slots(case, geo):
     """CS = HX HY HZ of the tile the library reports: the halo'd extent a workgroup stages per chunk.  pixie_conv_tile_geometry
-    reports TX, TY, TZ and not the halo extents, so the halo formula of the launch plan (conv3d_f16x3.hip, where the plan sets
+    reports TX, TY, TZ and not the halo extents, so the halo formula of the launch plan (conv_plan.h, where conv_plan() sets
     p.HX / p.HY / p.HZ) is restated here: the asserted n checks the cases against that formula, not the formula itself."""
     if case.sub:      # the tile lies over the stored voxels; one voxel of halo on the side the parity reads, x on both
         return (geo["TX"] + 2) * (geo["TY"] + 1) * (geo["TZ"] + 1)

@@ -1,4 +1,4 @@
-"""The algebra behind the sub-pixel up-convolutions (conv3d_f16x3.hip, pack_weights_subpixel_kernel), in float64 on the CPU:
+"""The algebra behind the sub-pixel up-convolutions (conv_pack_kernels.h, pack_weights_subpixel_kernel), in float64 on the CPU:
 a 3^3 convolution (padding 1) of a nearest-x2 upsampled tensor equals eight 2x2x2-tap convolutions of the STORED tensor, one
 per output parity, with the taps that read the same stored voxel summed beforehand.  Pins the tap grouping, the tap origin
 per parity, the zero padding and the odd-grid crop."""

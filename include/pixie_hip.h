@@ -397,6 +397,20 @@ int64_t pixie_unet_workspace_bytes(pixie_unet* h, int d, int hh, int w);
  * synchronises the stream once to read the normalisation bounds; later calls are launch-only. */
 int pixie_unet_forward(pixie_unet* h, const float* d_feat, const float* d_proj0, int d, int hh, int w, float* d_out,
                        void* d_workspace, int64_t workspace_bytes, void* stream);
+/* Two networks over ONE input on one stream: the outputs of pixie_unet_forward(h0, d_feat, NULL, ..., d_out0, ...) and of the same
+ * call for h1, bit for bit, from one interleaved sequence of launches.  Both plans are walked into launch lists
+ * (csrc/launch_list.h), then launched as: h0's full-resolution encoder section, h1's, the levels below full resolution of both
+ * zipped -- two launches at the same position that run the same kernel on the same grid go out as one launch of that kernel's
+ * grouped form (the split-K reduces, the statistics finalisers and the conv instantiations of conv16_group_kernel()'s table in
+ * csrc/conv3d_f16x3.hip have one) --, h0's decoder section, h1's.  h1 takes over the
+ * input statistics h0's pass computes.  Networks that differ in shape or precision only group less.  Both workspaces are in use
+ * at once: each at least pixie_unet_workspace_bytes of its network, distinct.  No d_proj0 route; the handles' "graph" option
+ * does not apply (the sequence is capturable by the caller).  launch_counts (optional): the launches of the two single passes,
+ * the launches issued, how many of those are grouped, and how many of the grouped ones are convolutions (launches with dynamic
+ * LDS).  PIXIE_UNET_PAIR_GROUP=0 in the environment: zipped, nothing grouped. */
+int pixie_unet_forward_pair(pixie_unet* h0, pixie_unet* h1, const float* d_feat, int d, int hh, int w, float* d_out0, float* d_out1,
+                            void* d_workspace0, int64_t workspace0_bytes, void* d_workspace1, int64_t workspace1_bytes, void* stream,
+                            int32_t launch_counts[4]);
 /* Options.  "graph" = 1: pixie_unet_forward records its launch sequence the first time it sees a combination of
  * (d_feat, d_proj0, d_out, d_workspace) pointers and replays it as ONE hipGraphLaunch on later calls with the same pointers
  * (a caller that keeps its buffers; up to 4 combinations are kept; pixie_unet_set_param invalidates them).  Needs a

@@ -320,6 +320,7 @@ SIGNATURES = {
     "pixie_unet_workspace_bytes": (_I64, [_VP, _I, _I, _I]),
     "pixie_unet_set_option": (_I, [_VP, _S, _I]),
     "pixie_unet_forward": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I64, _VP]),
+    "pixie_unet_forward_pair": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP]),
     "pixie_combine_class_ids": (_I, [_VP, _I, _VP, _I64, _VP, _VP]),
     "pixie_combine_predictions": (_I, [_VP, _I, _VP, _I64, _VP, _VP, _VP]),
     "pixie_voxel_grid_to_ncdhw": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),

@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "../../include/pixie_hip.h"
+#include "launch_record.h"
 
 namespace pixie {
 hipError_t allow_max_dynamic_lds(const void* kern) {
@@ -19,6 +20,11 @@ hipError_t allow_max_dynamic_lds(const void* kern) {
     e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) done.insert({kern, dev});
     return e;
+}
+
+LaunchList*& launch_recorder() {
+    static thread_local LaunchList* rec = nullptr;
+    return rec;
 }
 
 std::string& last_error_ref() {

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "conv16_device.h"
+#include "launch_record.h"
 
 namespace pixie {
 
@@ -42,7 +43,9 @@ namespace pixie {
 // quartets into two LDS buffers: chunk 0 by all 512 threads, then per chunk k quartet 0 stages its half of chunk k + 1's slots
 // and multiplies chunk k, quartet 1 multiplies first and stages afterwards, one barrier per chunk.  Waves w and w + 4 share a
 // SIMD, so each SIMD has one wave in the tap loop while the other stages.
-template <int KS, int MB, int NB, bool EX = false, bool SP = false, int SK = 0, bool PAIR = false>
+// GRP ("grouped twin", launch_list.h): the launch carries two argument sets behind a doubled grid z; A is the set of this workgroup
+// and the split-K slice index is blockIdx.z within its half.  Everything else is the single form's, statement for statement.
+template <int KS, int MB, int NB, bool EX = false, bool SP = false, int SK = 0, bool PAIR = false, bool GRP = false>
 __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     static_assert(!PAIR || (MB == 2 && !EX && !SP && SK == 0), "pair form: the plain f16x3 body with 64 c_out per quartet");
     static_assert(!SP || (KS == 3 && NB == 4 && !EX), "sub-pixel path: 3^3, two x parities x two voxel blocks per wave");
@@ -52,6 +55,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     constexpr int NW = 4, NT = 64 * NW;     // (an 8-wave, one-workgroup-per-CU tile was measured in round 4: 1.350 vs 1.323 ms, profiles/r4k_conv_eight_wave_tile_rejected.txt)
     const int bufsz = 4 * A.CS;            // one buffer: hi[2][CS], lo[2][CS]
 
+    const unsigned zslice = GRP ? blockIdx.z - (blockIdx.z >= (gridDim.z >> 1) ? (gridDim.z >> 1) : 0u) : blockIdx.z;   // split-K slice
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int quartet = PAIR ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;   // wave-uniform
@@ -145,7 +149,7 @@ __device__ __forceinline__ void conv3d_f16x3_body(const Conv16Args& A) {
     // ---- the chunk loop, then the folded skip convolution where the kernel has one ----
     float inv2 = 0.0f;   // unscale factor after a folded skip convolution
     {
-        const int c_begin = A.partial ? (int)blockIdx.z * A.chunks_per_slice * 16 : 0;
+        const int c_begin = A.partial ? (int)zslice * A.chunks_per_slice * 16 : 0;
         const int c_end = A.partial ? min(A.cin, c_begin + A.chunks_per_slice * 16) : A.cin;
         if constexpr (PAIR) {
             // Half-steps.  A quartet always stages its own half of a chunk's slots, [0, half) or [half, CS): at h = -1 both stage
@@ -211,6 +215,19 @@ __global__ __launch_bounds__(256, 2) void conv3d_exact_kernel(Conv16Args A) {
 template <int MB>
 __global__ __launch_bounds__(256, 2) void conv3d_f16x3_subpixel_kernel(Conv16Args A) {
     conv3d_f16x3_body<3, MB, 4, false, true>(A);
+}
+// Grouped twins (launch_list.h, pixie_unet_forward_pair): the launches of two networks that run the same instantiation on the same
+// grid, as one launch.  Workgroups with blockIdx.z in the upper half of the grid take the second argument set (wave-uniform, the
+// arguments stay scalar loads from the kernel argument segment); blockIdx.x and blockIdx.y mean what they mean in the single form.
+// Instantiations of their own, like the skip kernels: the single forms' code is not touched.  Which launches have one is
+// conv16_group_kernel()'s table (conv3d_f16x3.hip).
+template <int KS, int MB, int NB>
+__global__ __launch_bounds__(256, 2) void conv3d_f16x3_group_kernel(Group2<Conv16Args> G) {
+    conv3d_f16x3_body<KS, MB, NB, false, false, 0, false, true>(G.a[blockIdx.z >= (gridDim.z >> 1) ? 1 : 0]);
+}
+template <int MB>
+__global__ __launch_bounds__(256, 2) void conv3d_f16x3_subpixel_group_kernel(Group2<Conv16Args> G) {
+    conv3d_f16x3_body<3, MB, 4, false, true, 0, false, true>(G.a[blockIdx.z >= (gridDim.z >> 1) ? 1 : 0]);
 }
 // The dominant layer of the BASELINE network -- 64 -> 64 channels, 3^3, stride 1, on >= 128^3 voxels (the full-resolution
 // level: 41 % of a scene's FLOPs at 128^3; the 64^3 level has the same channel counts and stays on the template) -- under its own symbol, so that `rocprofv3 --kernel-trace --stats` reports it as

@@ -1,12 +1,12 @@
 // pixie_amd/csrc/conv16_epilogue.h -- FRAGMENT of conv3d_f16x3_body (conv16_body.h), included inside it as its last statements: the
 // epilogue.  No include guard: included once.
 // acc -> unscale, + bias (+ folded-skip bias) (+ residual) -> A.out; or, in a split-K slice (A.partial), the raw unscaled sums ->
-// A.partial[blockIdx.z], after which the fragment RETURNS from the body.  With A.stats it leaves the per-channel partial sums of
+// A.partial[zslice], after which the fragment RETURNS from the body.  With A.stats it leaves the per-channel partial sums of
 // this tile in A.stats and the tile's |x|max in *A.out_amax.  Interior tiles with the LDS reserved (A.epi_lds) transpose the
 // accumulators through LDS into rows of 4 x-consecutive voxels per lane (`full`); every other tile stores from the MFMA layout.
 //   template parameters read:  EX, SP, SK, PAIR, MB, NB
 //   names of the body read:    A, acc, ex, inv2 (SK != 0), NW, smem16, cout0, OSP, valid, ovox, lane, l31, kh, wave, quartet, qtid,
-//                              ox0, oy0, oz0, py, pz
+//                              ox0, oy0, oz0, py, pz, zslice
 //   writes:                    global memory (A.out or A.partial, A.stats, *A.out_amax); LDS: the activation tile is dead and
 //                              reused for the transposing area and the statistics partials `red`
 //   barriers:                  `full` path: one, before the first LDS write (every wave is done with the tile).  Other path: one
@@ -19,7 +19,7 @@
     // to *out_amax; pixie_stats_finalize adds the tiles up in fp64.  That replaces one full read of the tensor.
     const float inv = EX ? 1.0f : (SK != 0 ? inv2 : __uint_as_float(A.w16[0].x) * pow2i(-ex));
     if (A.partial) {   // split-K slice: raw partial sums; bias, residual and statistics belong to splitk_reduce_kernel
-        float* dst = A.partial + (size_t)blockIdx.z * A.cout * OSP;
+        float* dst = A.partial + (size_t)zslice * A.cout * OSP;
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll

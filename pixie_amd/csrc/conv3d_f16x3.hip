@@ -45,6 +45,7 @@
 #include "common.h"
 #include "conv_plan.h"
 #include "conv_launch.h"
+#include "launch_record.h"
 #include "conv16_device.h"
 #include "conv16_body.h"
 #include "conv_stat_kernels.h"
@@ -83,6 +84,28 @@ static ConvKernel conv16_kernel(const ConvPlan& p, bool skip = false, int skip_c
     return nullptr;
 }
 
+// The grouped twin of conv16_kernel()'s answer (conv16_body.h), null where the launch has none.  The table holds the instantiations
+// the shipped networks launch below full resolution whose grouped launch, measured there against two single launches, is not
+// slower by more than 2 % (profiles/unet_pair_ab_ms_per_step.txt): <3,2,4>, sub-pixel <2>, <1,2,2>, <1,2,1>.  Measured and taken
+// out: <3,2,2> (+6 % and +10 % at its two shapes), <3,2,1> (+6 % to +14 % at three of four), <1,2,4> (+13 % at the 32^3 level),
+// the folded-skip form of <3,2,4> (+1.2 % in one trace, +3.0 % in the next).  Never in it: the 32-channel-block instantiations
+// (MB = 1), which those networks do not launch there (<3,1,4> would also lose a wave of occupancy to its twin), the 8-wave pair
+// form, the exact-fp32 kernels.  A launch without a twin stays two launches.
+using ConvGroupKernel = void (*)(Group2<Conv16Args>);
+template <int KS, int MB, int NB> static ConvGroupKernel conv16_group_pick() {
+    if constexpr ((KS == 3 && MB == 2 && NB == 4) || (KS == 1 && MB == 2 && (NB == 2 || NB == 1))) return conv3d_f16x3_group_kernel<KS, MB, NB>;
+    else return nullptr;
+}
+static ConvGroupKernel conv16_group_kernel(const ConvPlan& p, bool skip = false) {
+    if (p.path == CONV_F16X3_SUBPIXEL) return p.MB == 2 ? conv3d_f16x3_subpixel_group_kernel<2> : nullptr;
+    if (p.fullres || p.path == CONV_EXACT_TILED || skip) return nullptr;
+#define PX_CONV16_PICK(KS_, MB_, NB_)                \
+    if (p.KS == KS_ && p.MB == MB_ && p.NB == NB_) return conv16_group_pick<KS_, MB_, NB_>();
+    PX_CONV_VARIANTS(PX_CONV16_PICK)
+#undef PX_CONV16_PICK
+    return nullptr;
+}
+
 // The pair form of a planned launch: conv_pair_lds_bytes() (conv_plan.h) decides it from the plan; returns the launch's dynamic LDS
 // bytes, 0 = the launch keeps the 4-wave kernel.
 #ifdef PIXIE_DIAG
@@ -102,11 +125,13 @@ static ConvKernel conv16_pair_kernel(const ConvPlan& p) {
     return nullptr;
 }
 
-static int launch(ConvKernel kern, const ConvPlan& p, const Conv16Args& a, hipStream_t st, size_t pair_lds = 0) {
+static int launch(ConvKernel kern, const ConvPlan& p, const Conv16Args& a, hipStream_t st, size_t pair_lds = 0, ConvGroupKernel twin = nullptr) {
     PX_REQUIRE(kern != nullptr, "conv: no kernel variant for ksize=%d MB=%d NB=%d", p.KS, p.MB, p.NB);
     PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    if (pair_lds) hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y / 2, 1), dim3(512), pair_lds, st, a);
-    else hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), p.lds_bytes, st, a);
+    if (twin && launch_recorder()) PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(twin)));
+    if (pair_lds) px_launch(kern, dim3(p.grid_x, p.grid_y / 2, 1), dim3(512), pair_lds, st, a);
+    else if (twin) px_launch_grouped(kern, twin, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), p.lds_bytes, st, a);
+    else px_launch(kern, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), p.lds_bytes, st, a);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -157,7 +182,9 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
     PX_REQUIRE(p.refusal != CONV_BAD_LDS, "f16x3 conv: tile needs %zu B of LDS", p.lds_bytes);
     PX_REQUIRE(p.f16x3(), "f16x3 conv: bad sizes");
     const size_t pair_lds = conv_pair_lds(p, a.sk_w16 != nullptr);
-    if (int rc = launch(pair_lds ? conv16_pair_kernel(p) : conv16_kernel(p, a.sk_w16 != nullptr, a.sk_c0), p, a, st, pair_lds)) return rc;
+    if (int rc = launch(pair_lds ? conv16_pair_kernel(p) : conv16_kernel(p, a.sk_w16 != nullptr, a.sk_c0), p, a, st, pair_lds,
+                        pair_lds ? nullptr : conv16_group_kernel(p, a.sk_w16 != nullptr)))
+        return rc;
     if (p.slices == 1) return 0;
     const long osp = (long)a.OD * a.OH * a.OW, n_elems = (long)a.cout * osp;
     if (d->d_out_stats) {
@@ -165,13 +192,13 @@ int conv3d_f16x3_forward(const pixie_conv_desc* d, const ConvPlan& p, hipStream_
         double* rstats = reinterpret_cast<double*>(d->d_out_stats);
         PX_REQUIRE((reinterpret_cast<size_t>(rstats) & 7) == 0, "f16x3 conv: d_out_stats of a split-K launch must be 8-byte aligned");
         const bool vec = osp % 4 == 0 && ((reinterpret_cast<size_t>(a.partial) | reinterpret_cast<size_t>(a.residual) | reinterpret_cast<size_t>(a.out)) & 15) == 0;
-        if (vec) hipLaunchKernelGGL(splitk_reduce_stats_kernel<true>, rgrid, dim3(256), 0, st, a.partial, p.slices, n_elems, osp, a.bias, a.residual,
-                                    a.out, rstats, d->d_out_amax);
-        else hipLaunchKernelGGL(splitk_reduce_stats_kernel<false>, rgrid, dim3(256), 0, st, a.partial, p.slices, n_elems, osp, a.bias, a.residual,
-                                a.out, rstats, d->d_out_amax);
+        if (vec) px_launch_grouped(splitk_reduce_stats_kernel<true>, splitk_reduce_stats_group_kernel<true>, rgrid, dim3(256), 0, st, a.partial, p.slices,
+                                   n_elems, osp, a.bias, a.residual, a.out, rstats, d->d_out_amax);
+        else px_launch_grouped(splitk_reduce_stats_kernel<false>, splitk_reduce_stats_group_kernel<false>, rgrid, dim3(256), 0, st, a.partial, p.slices,
+                               n_elems, osp, a.bias, a.residual, a.out, rstats, d->d_out_amax);
     } else {
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, p.slices, n_elems, osp,
-                           a.bias, a.residual, a.out);
+        px_launch(splitk_reduce_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, a.partial, p.slices, n_elems, osp,
+                  a.bias, a.residual, a.out);
     }
     PX_CHECK_HIP(hipGetLastError());
     return 0;
@@ -244,7 +271,7 @@ extern "C" int pixie_conv_skip_foldable(const pixie_conv_desc* d) { return plan_
 extern "C" int pixie_stats_finalize(const float* d_stats, const pixie_conv_desc* d, double* d_sums, void* stream) {
     PX_REQUIRE(d_stats && d && d_sums, "pixie_stats_finalize: null argument");
     // the tile (or segment) count comes from the plan conv3d_f16x3_forward launched with
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), stat_parts(plan_of(d), d_stats), d_sums);
+    px_launch(stats_finalize_kernel, dim3((unsigned)d->c_out), dim3(256), 0, as_stream(stream), stat_parts(plan_of(d), d_stats), d_sums);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -261,8 +288,8 @@ extern "C" int pixie_stats_norm_finalize(const float* d_stats0, const pixie_conv
     const StatParts none{nullptr, 0, 0, 0, 0};
     const StatParts p0 = d_stats0 ? stat_parts(plan_of(desc0), d_stats0) : none;
     const StatParts p1 = d_stats1 ? stat_parts(plan_of(desc1), d_stats1) : none;
-    hipLaunchKernelGGL(stats_norm_finalize_kernel, dim3((unsigned)(mode == 0 ? channels : groups)), dim3(256), 0, as_stream(stream), p0, d_sums0, c0,
-                       p1, d_sums1, channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
+    px_launch_grouped(stats_norm_finalize_kernel, stats_norm_finalize_group_kernel, dim3((unsigned)(mode == 0 ? channels : groups)), dim3(256), 0,
+                      as_stream(stream), p0, d_sums0, c0, p1, d_sums1, channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

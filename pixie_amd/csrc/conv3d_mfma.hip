@@ -25,6 +25,7 @@
 #include "common.h"
 #include "conv_launch.h"
 #include "conv_plan.h"
+#include "launch_record.h"
 
 namespace pixie {
 
@@ -217,7 +218,7 @@ template <int KS, int MB, int NB, int CK>
 static int launch_variant(const ConvArgs& a, size_t lds_bytes, dim3 grid, hipStream_t st) {
     auto kern = conv3d_mfma_kernel<KS, MB, NB, CK>;
     PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
+    px_launch(kern, grid, dim3(256), lds_bytes, st, a);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

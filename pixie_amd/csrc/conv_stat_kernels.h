@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_plan.h"
+#include "launch_record.h"
 
 namespace pixie {
 
@@ -48,40 +49,22 @@ __global__ __launch_bounds__(256) void stats_norm_finalize_kernel(StatParts P0, 
                                                                   double spatial, int mode, int groups, double eps,
                                                                   const float* __restrict__ weight, const float* __restrict__ bias,
                                                                   float* __restrict__ a, float* __restrict__ b) {
-    __shared__ double r[8];
-    const int cpg = mode == 0 ? 1 : channels / groups;
-    const int first = blockIdx.x * cpg;
-    double s1 = 0.0, s2 = 0.0;
-    for (int k = first; k < first + cpg; ++k) {
-        const bool in0 = k < c0;
-        const StatParts& P = in0 ? P0 : P1;
-        double* sums = in0 ? sums0 : sums1;
-        const int kc = in0 ? k : k - c0;
-        double t1, t2;
-        if (P.n > 0) {
-            block_channel_sums(P, kc, r, t1, t2);
-            if (threadIdx.x == 0) { sums[2 * kc] = t1; sums[2 * kc + 1] = t2; }
-        } else {
-            t1 = sums[2 * kc]; t2 = sums[2 * kc + 1];
-        }
-        s1 += t1; s2 += t2;
-    }
-    const double cnt = mode == 0 ? spatial : spatial * cpg;
-    const double mean = s1 / cnt;
-    double var = s2 / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
-    for (int k = first + threadIdx.x; k < first + cpg; k += 256) {
-        if (mode == 0) {
-            a[k] = (float)rstd;
-            b[k] = (float)(-mean * rstd);
-        } else {
-            const double w = weight ? (double)weight[k] : 1.0;
-            const double bb = bias ? (double)bias[k] : 0.0;
-            a[k] = (float)(rstd * w);
-            b[k] = (float)(bb - mean * rstd * w);
-        }
-    }
+#include "conv_stat_norm_finalize.h"
+}
+// Grouped twin (launch_list.h): the same launch for two networks at once, blockIdx.z picks the argument set.  The members are the
+// single form's parameters in order.
+struct StatsNormFinalizeArgs {
+    StatParts P0; double* sums0; int c0; StatParts P1; double* sums1; int channels; double spatial; int mode, groups; double eps;
+    const float* weight; const float* bias; float* a; float* b;
+};
+__global__ __launch_bounds__(256) void stats_norm_finalize_group_kernel(Group2<StatsNormFinalizeArgs> G) {
+    const StatsNormFinalizeArgs& A = G.a[blockIdx.z];
+    const StatParts& P0 = A.P0; const StatParts& P1 = A.P1;
+    double* sums0 = A.sums0; double* sums1 = A.sums1;
+    const int c0 = A.c0, channels = A.channels, mode = A.mode, groups = A.groups;
+    const double spatial = A.spatial, eps = A.eps;
+    const float* weight = A.weight; const float* bias = A.bias; float* a = A.a; float* b = A.b;
+#include "conv_stat_norm_finalize.h"
 }
 
 // out = sum_s partial[s] + bias (+ residual), slices added in a fixed order (deterministic split-K)
@@ -109,69 +92,20 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* __restrict__ partial, int slices, long n_elems, long osp,
                                                                   const float* __restrict__ bias, const float* residual, float* out,
                                                                   double* __restrict__ stats, unsigned* out_amax) {
-    const int c = blockIdx.y;
-    const long seg0 = (long)blockIdx.x * kReduceSeg;
-    const size_t base = (size_t)c * osp;
-    const float bv = bias ? bias[c] : 0.0f;
-    double s1 = 0.0, s2 = 0.0;
-    float mx = 0.0f;
-    if (VEC) {
-#pragma unroll
-        for (int k = 0; k < kReduceSeg / 1024; ++k) {
-            const long j = seg0 + k * 1024 + (long)threadIdx.x * 4;
-            if (j < osp) {
-                const size_t i = base + j;
-                float4 v = *reinterpret_cast<const float4*>(partial + i);
-                for (int s = 1; s < slices; ++s) {
-                    const float4 q = *reinterpret_cast<const float4*>(partial + (size_t)s * n_elems + i);
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-                }
-                if (bias) { v.x += bv; v.y += bv; v.z += bv; v.w += bv; }
-                if (residual) {
-                    const float4 q = *reinterpret_cast<const float4*>(residual + i);
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-                }
-                *reinterpret_cast<float4*>(out + i) = v;
-                const double x = v.x, y = v.y, z = v.z, w = v.w;
-                s1 += (x + y) + (z + w);
-                s2 += (x * x + y * y) + (z * z + w * w);
-                mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int k = 0; k < kReduceSeg / 256; ++k) {
-            const long j = seg0 + k * 256 + threadIdx.x;
-            if (j < osp) {
-                const size_t i = base + j;
-                float v = partial[i];
-                for (int s = 1; s < slices; ++s) v += partial[(size_t)s * n_elems + i];
-                if (bias) v += bv;
-                if (residual) v += residual[i];
-                out[i] = v;
-                const double x = v;
-                s1 += x; s2 += x * x; mx = fmaxf(mx, fabsf(v));
-            }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-        mx = fmaxf(mx, __shfl_down(mx, off, 64));
-    }
-    __shared__ double r[8];
-    __shared__ float rmx[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { r[2 * wave] = s1; r[2 * wave + 1] = s2; rmx[wave] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* dst = stats + ((size_t)c * gridDim.x + blockIdx.x) * 2;
-        dst[0] = r[0] + r[2] + r[4] + r[6];
-        dst[1] = r[1] + r[3] + r[5] + r[7];
-        const unsigned m = __float_as_uint(fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3])));
-        // the slot only grows: a stale read can only be too small, and then costs the atomic it would have cost anyway
-        if (out_amax && m > __hip_atomic_load(out_amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out_amax, m);
-    }
+#include "conv_stat_splitk_reduce.h"
+}
+// Grouped twin (launch_list.h): two networks' reduces of the same shape in one launch, blockIdx.z picks the argument set
+struct SplitkReduceStatsArgs {
+    const float* partial; int slices; long n_elems, osp; const float* bias; const float* residual; float* out; double* stats; unsigned* out_amax;
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void splitk_reduce_stats_group_kernel(Group2<SplitkReduceStatsArgs> G) {
+    const SplitkReduceStatsArgs& A = G.a[blockIdx.z];
+    const float* partial = A.partial; const float* bias = A.bias; const float* residual = A.residual;
+    const int slices = A.slices;
+    const long n_elems = A.n_elems, osp = A.osp;
+    float* out = A.out; double* stats = A.stats; unsigned* out_amax = A.out_amax;
+#include "conv_stat_splitk_reduce.h"
 }
 
 // |x|max of a tensor as float bits (non-negative floats order like unsigned integers); caller zeroes the slot

@@ -31,6 +31,7 @@
 #include "common.h"
 #include "conv_launch.h"
 #include "conv_plan.h"
+#include "launch_record.h"
 
 namespace pixie {
 // internal entry points of unet_ops.hip (the launches of pixie_channel_stats / pixie_norm_finalize without their set-up work)
@@ -299,6 +300,14 @@ struct Exec {
     int slot_next = 0, slot_cap = 0;
     double* zsums = nullptr;
     int64_t zsum_next = 0, zsum_cap = 0;
+    // record mode (pixie_unet_forward_pair): the launch sites append to this list instead of launching (launch_record.h); the walk
+    // marks the section.  Weight packing is no part of a pass and still launches.
+    LaunchList* rec = nullptr;
+    // the statistics pass over the caller's input: `in_ptr` is that tensor; what the pass left (in_sums, in_slot) can serve a second
+    // network that reads the same tensor behind this one on the stream (share_sums, share_slot: set = take these, launch nothing)
+    const float* in_ptr = nullptr;
+    double* in_sums = nullptr; uint32_t* in_slot = nullptr;
+    double* share_sums = nullptr; uint32_t* share_slot = nullptr;
 
     TP make(int c, int d, int h, int w) {
         auto t = std::make_shared<Tens>();
@@ -373,11 +382,14 @@ struct Exec {
     void stats(const TP& t) {                  // channel sums + |x|max by a pass over the tensor (only where no conv produced them)
         if (t->has_sums || t->partials_off >= 0) return;
         t->has_sums = true;
+        const bool input = t->off < 0 && in_ptr && t->p == in_ptr;
+        if (input && share_slot) { t->sums = share_sums; t->slot = share_slot; return; }
         if (!dry && zsum_next + 2 * t->c > zsum_cap) fail("pixie_unet_forward: out of statistics space (internal sizing error)");
         t->sums = dry ? nullptr : zsums + zsum_next;      // the kernel adds into zeroed memory (fp64 atomics)
         zsum_next += 2 * t->c;
         t->slot = new_slot();
         if (!dry) ok(channel_stats_prezeroed(t->p, t->c, t->spatial(), t->sums, t->slot, as_stream(stream)), "pixie_channel_stats");
+        if (input) { in_sums = t->sums; in_slot = t->slot; }
     }
     struct AB { std::shared_ptr<Scratch> mem; float* a; float* b; };
     // The prologue affine of a normalisation over th.cat(parts) (never materialised; statistics are read where they lie).
@@ -553,12 +565,16 @@ struct Exec {
         if (b.kind == RES) return res(b, parts);
         const TP& x = parts[0];
         if (b.kind == ATTN) return attn(b, x);
-        if (b.kind == DOWN) { ConvOpt o; o.stride = 2; return conv({x}, b.prefix + ".op", b.cout, 3, o); }
+        if (b.kind == DOWN) {
+            if (rec && x->d == net->cfg.grid_size) rec->section = SEC_INNER;      // the inner section starts at the first stride-2 conv
+            ConvOpt o; o.stride = 2; return conv({x}, b.prefix + ".op", b.cout, 3, o);
+        }
         if (b.kind == UP) {
             // `up_to`: the skip tensor this output will be concatenated with; on odd grids it is one voxel smaller than
             // 2 * sp per axis and the reference crops h[..., :-1] (diffusion_network.py:925-930)
             ConvOpt o; o.upsample = true;
             if (up_to) { o.out_d = up_to->d; o.out_h = up_to->h; o.out_w = up_to->w; }
+            if (rec && (up_to ? up_to->d : 2 * x->d) == net->cfg.grid_size) rec->section = SEC_FULLRES;   // ... and ends before the up-conv back to full resolution
             return conv({x}, b.prefix + ".conv", b.cout, 3, o);
         }
         fail("pixie_unet: unexpected block kind");
@@ -697,6 +713,37 @@ Sized size_pass(pixie_unet* net, int D, int H, int W, bool from_proj0) {
     return r;
 }
 
+// One pass: the head of the workspace cleared, then the plan walk.  `rec`: append the launches to this list instead of launching
+// them.  `share`: a pass over the same d_feat that goes out on the stream before this one; its input statistics are taken over.
+void run_pass(pixie_unet* h, const float* d_feat, const float* d_proj0, int d, int hh, int w, float* d_out, void* d_workspace, int64_t workspace_bytes,
+              const Sized& sized, void* stream, LaunchList* rec = nullptr, Exec* ex_out = nullptr, const Exec* share = nullptr) {
+    Exec local;
+    Exec& ex = ex_out ? *ex_out : local;
+    ex.net = h; ex.dry = false; ex.stream = stream; ex.rec = rec;
+    ex.in_ptr = d_feat;
+    if (share && share->in_ptr == d_feat && share->in_slot) { ex.share_sums = share->in_sums; ex.share_slot = share->in_slot; }
+    const int64_t slot_bytes = slot_region_bytes(sized.slots), head_bytes = slot_bytes + zsum_region_bytes(sized.zsum_doubles);
+    ex.slots = static_cast<uint32_t*>(d_workspace);
+    ex.slot_cap = sized.slots;
+    ex.zsums = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + slot_bytes);
+    ex.zsum_cap = sized.zsum_doubles;
+    struct Recording {   // the launch sites look at the calling thread's recorder
+        LaunchList* before;
+        explicit Recording(LaunchList* r) : before(launch_recorder()) { launch_recorder() = r; }
+        ~Recording() { launch_recorder() = before; }
+    } recording(rec);
+    if (rec) rec->section = SEC_FULLRES;
+    // Zeroed by a KERNEL, not hipMemsetAsync: as a node of a captured graph the memset did not reliably complete before
+    // the kernels that follow it on ROCm 7.2 (replays of the f16x3 pass, whose first kernel already adds into this
+    // region, gave wrong results at random once the workspace held a previous replay's values:
+    // scripts/unet_soak.py, profiles/r3i_graph_replay_bisect.txt).  A kernel node has ordinary dependencies.
+    px_launch(zero_head_kernel, dim3((unsigned)((head_bytes / 16 + 255) / 256)), dim3(256), 0, as_stream(stream),
+              static_cast<uint4*>(d_workspace), head_bytes / 16);
+    if (!rec && hipGetLastError() != hipSuccess) fail("pixie_unet_forward: clearing the workspace head failed");
+    ex.arena.reset(static_cast<char*>(d_workspace) + head_bytes, workspace_bytes - head_bytes);
+    TP out = ex.forward(d_feat, d_proj0, d, hh, w, d_out);
+}
+
 template <class F> int guarded(F f) {
     try { return f(); }
     catch (const std::exception& e) { return set_error("%s", e.what()); }
@@ -788,24 +835,7 @@ extern "C" int pixie_unet_forward(pixie_unet* h, const float* d_feat, const floa
         const auto sized = size_pass(h, d, hh, w, d_proj0 != nullptr);
         if (workspace_bytes < sized.bytes)
             fail("pixie_unet_forward: workspace of %lld bytes, this grid needs %lld (pixie_unet_workspace_bytes)", (long long)workspace_bytes, (long long)sized.bytes);
-        auto launch_all = [&] {
-            Exec ex;
-            ex.net = h; ex.dry = false; ex.stream = stream;
-            const int64_t slot_bytes = slot_region_bytes(sized.slots), head_bytes = slot_bytes + zsum_region_bytes(sized.zsum_doubles);
-            ex.slots = static_cast<uint32_t*>(d_workspace);
-            ex.slot_cap = sized.slots;
-            ex.zsums = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + slot_bytes);
-            ex.zsum_cap = sized.zsum_doubles;
-            // Zeroed by a KERNEL, not hipMemsetAsync: as a node of a captured graph the memset did not reliably complete before
-            // the kernels that follow it on ROCm 7.2 (replays of the f16x3 pass, whose first kernel already adds into this
-            // region, gave wrong results at random once the workspace held a previous replay's values:
-            // scripts/unet_soak.py, profiles/r3i_graph_replay_bisect.txt).  A kernel node has ordinary dependencies.
-            hipLaunchKernelGGL(zero_head_kernel, dim3((unsigned)((head_bytes / 16 + 255) / 256)), dim3(256), 0, as_stream(stream),
-                               static_cast<uint4*>(d_workspace), head_bytes / 16);
-            if (hipGetLastError() != hipSuccess) fail("pixie_unet_forward: clearing the workspace head failed");
-            ex.arena.reset(static_cast<char*>(d_workspace) + head_bytes, workspace_bytes - head_bytes);
-            TP out = ex.forward(d_feat, d_proj0, d, hh, w, d_out);
-        };
+        auto launch_all = [&] { run_pass(h, d_feat, d_proj0, d, hh, w, d_out, d_workspace, workspace_bytes, sized, stream); };
         if (h->use_graph) {
             for (size_t i = 0; i < h->replays.size(); ++i) {
                 const pixie_unet::Replay& r = h->replays[i];
@@ -835,6 +865,46 @@ extern "C" int pixie_unet_forward(pixie_unet* h, const float* d_feat, const floa
             if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(graph); fail("pixie_unet_forward: hipGraphInstantiate failed"); }
             if (h->replays.size() >= pixie_unet::kMaxReplays) h->drop_replay(0);
             h->replays.push_back(pixie_unet::Replay{d_feat, d_proj0, d_out, d_workspace, d, h->epoch, graph, exec});
+        }
+        return 0;
+    });
+}
+
+extern "C" int pixie_unet_forward_pair(pixie_unet* h0, pixie_unet* h1, const float* d_feat, int d, int hh, int w, float* d_out0, float* d_out1,
+                                       void* d_workspace0, int64_t workspace0_bytes, void* d_workspace1, int64_t workspace1_bytes, void* stream,
+                                       int32_t* launch_counts) {
+    PX_REQUIRE(h0 && h1 && h0 != h1 && d_feat && d_out0 && d_out1 && d_workspace0 && d_workspace1, "pixie_unet_forward_pair: null argument, or one handle twice");
+    PX_REQUIRE(d_out0 != d_out1 && d_workspace0 != d_workspace1, "pixie_unet_forward_pair: the two networks need outputs and workspaces of their own");
+    pixie_unet* hs[2] = {h0, h1};
+    for (pixie_unet* h : hs)
+        PX_REQUIRE(d == h->cfg.grid_size && hh == d && w == d,
+                   "pixie_unet_forward_pair: a network was built for a %d^3 grid (its LayerNorm parameters have that shape), got %d x %d x %d", h->cfg.grid_size, d, hh, w);
+    return guarded([&] {
+        float* outs[2] = {d_out0, d_out1};
+        void* wss[2] = {d_workspace0, d_workspace1};
+        const int64_t wsb[2] = {workspace0_bytes, workspace1_bytes};
+        Sized sized[2];
+        for (int k = 0; k < 2; ++k) {
+            sized[k] = size_pass(hs[k], d, hh, w, false);
+            if (wsb[k] < sized[k].bytes)
+                fail("pixie_unet_forward_pair: workspace %d of %lld bytes, this grid needs %lld (pixie_unet_workspace_bytes)", k, (long long)wsb[k], (long long)sized[k].bytes);
+        }
+        for (pixie_unet* h : hs) refresh_bounds(h, stream);
+        // both walks in record mode (they pack what needs packing, on the stream, ahead of every launch of the pass) ...
+        LaunchList lists[2];
+        Exec ex[2];
+        for (int k = 0; k < 2; ++k)
+            run_pass(hs[k], d_feat, nullptr, d, hh, w, outs[k], wss[k], wsb[k], sized[k], stream, &lists[k], &ex[k], k ? &ex[0] : nullptr);
+        // ... then one stream of launches: the levels below full resolution go out zipped, grouped where the two match
+        int grouped = 0;
+        const char* pg = getenv("PIXIE_UNET_PAIR_GROUP");
+        const std::vector<LaunchRec> merged = merge_pair(lists[0], lists[1], &grouped, !(pg && pg[0] == '0'));
+        for (const LaunchRec& r : merged)
+            if (launch_rec(r, as_stream(stream)) != hipSuccess) fail("pixie_unet_forward_pair: a launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (launch_counts) {
+            launch_counts[0] = (int32_t)(lists[0].recs.size() + lists[1].recs.size()); launch_counts[1] = (int32_t)merged.size(); launch_counts[2] = grouped;
+            launch_counts[3] = 0;
+            for (const LaunchRec& r : merged) launch_counts[3] += r.net < 0 && r.lds > 0;   // of the small kernels none asks for dynamic LDS
         }
         return 0;
     });

@@ -12,6 +12,7 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "launch_record.h"
 
 namespace pixie {
 
@@ -326,7 +327,7 @@ static int launch_attention(const float* qkv, float* out, int T, hipStream_t st)
     // the attribute belongs to the (function, device) pair and a process may drive several devices: once per device
     // (not per launch: the call is not a stream operation and must stay out of HIP-graph captures)
     PX_CHECK_HIP(allow_max_dynamic_lds(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, dim3((T + ATT_BQ - 1) / ATT_BQ), dim3(ATT_WAVES * 64), lds, st, qkv, out, T);
+    px_launch(kern, dim3((T + ATT_BQ - 1) / ATT_BQ), dim3(ATT_WAVES * 64), lds, st, qkv, out, T);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -377,8 +378,8 @@ int channel_stats_prezeroed(const float* d_x, int channels, int64_t spatial, dou
     long seg = (spatial + splits - 1) / splits;
     seg = (seg + 3) & ~3L;  // keep float4 alignment of segment starts
     splits = (spatial + seg - 1) / seg;
-    hipLaunchKernelGGL(channel_sums_kernel, dim3((unsigned)splits, (unsigned)channels), dim3(256), 0, st, d_x, (long)spatial, seg, d_sums,
-                       reinterpret_cast<unsigned*>(d_amax));
+    px_launch(channel_sums_kernel, dim3((unsigned)splits, (unsigned)channels), dim3(256), 0, st, d_x, (long)spatial, seg, d_sums,
+              reinterpret_cast<unsigned*>(d_amax));
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -409,8 +410,8 @@ extern "C" int pixie_norm_finalize(const double* d_sums, int channels, int64_t s
                                    const float* d_weight, const float* d_bias, float* d_a, float* d_b, void* stream) {
     PX_REQUIRE(d_sums && d_a && d_b && channels > 0 && spatial > 0, "pixie_norm_finalize: bad arguments");
     PX_REQUIRE(mode == 0 || (mode == 1 && groups > 0 && channels % groups == 0), "pixie_norm_finalize: bad mode/groups");
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(cdiv(channels, 64)), dim3(64), 0, as_stream(stream), d_sums, channels,
-                       static_cast<const double*>(nullptr), channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
+    px_launch(norm_finalize_kernel, dim3(cdiv(channels, 64)), dim3(64), 0, as_stream(stream), d_sums, channels,
+              static_cast<const double*>(nullptr), channels, (double)spatial, mode, groups, eps, d_weight, d_bias, d_a, d_b);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -420,8 +421,8 @@ namespace pixie {
 int norm_finalize_cat(const double* d_sums0, int c0, const double* d_sums1, int c1, int64_t spatial, int mode, int groups, double eps,
                       const float* d_weight, const float* d_bias, float* d_a, float* d_b, hipStream_t st) {
     const int channels = c0 + c1;
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(cdiv(channels, 64)), dim3(64), 0, st, d_sums0, c0, d_sums1, channels, (double)spatial, mode, groups,
-                       eps, d_weight, d_bias, d_a, d_b);
+    px_launch(norm_finalize_kernel, dim3(cdiv(channels, 64)), dim3(64), 0, st, d_sums0, c0, d_sums1, channels, (double)spatial, mode, groups,
+              eps, d_weight, d_bias, d_a, d_b);
     PX_CHECK_HIP(hipGetLastError());
     return 0;
 }

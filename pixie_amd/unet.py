@@ -891,6 +891,79 @@ def _side_streams(device):
     return _SIDE_STREAMS[key]
 
 
+def _pair_call(seg_network, cont_network, x: torch.Tensor, counts=None):
+    """pixie_unet_forward_pair: both networks over one (C, D, H, W) input, one interleaved launch sequence on the current stream."""
+    hs, hc = seg_network._handle, cont_network._handle
+    d, h, w = (int(v) for v in x.shape[1:])
+    outs = [torch.empty((net.cfg.out_channels, d, h, w), device=x.device, dtype=torch.float32) for net in (seg_network, cont_network)]
+    nbytes = [hs.workspace_bytes(d, h, w), hc.workspace_bytes(d, h, w)]
+    wss = [torch.empty(n, device=x.device, dtype=torch.uint8) for n in nbytes]
+    check(hs.lib.pixie_unet_forward_pair(hs._h, hc._h, _ptr(x), d, h, w, _ptr(outs[0]), _ptr(outs[1]), _ptr(wss[0]), nbytes[0], _ptr(wss[1]), nbytes[1],
+                                         _lib.current_stream_ptr(), counts), "pixie_unet_forward_pair")
+    return outs[0], outs[1]
+
+
+def _forward_pair(seg_network, cont_network, feat_grid: torch.Tensor):
+    """The pair route of predict_material_field: ONE captured graph of pixie_unet_forward_pair for both networks, one replay per
+    scene.  On one stream the two networks' levels below full resolution are dependent chains of short launches; the pair call
+    zips the two chains and sends matching launches out as one (csrc/launch_list.h), with results equal bit for bit to the two
+    networks' own graphs.  Taken for one scene on the networks' device when both networks use the "c" executor with graphs on
+    (the caller has already ruled out dual_stream); PIXIE_UNET_PAIR=0 restores the two replays.  Returns None when not taken.
+    Keyed, captured and replayed as _PixieUNet._forward_graphed does it: first call eager, capture at the second, in place when
+    the caller's buffer comes back, on a private copy otherwise."""
+    if os.environ.get("PIXIE_UNET_PAIR", "1") == "0":
+        return None
+    nets = (seg_network, cont_network)
+    if not (feat_grid.is_cuda and feat_grid.dim() == 5 and feat_grid.shape[0] == 1 and seg_network is not cont_network):
+        return None
+    dev = feat_grid.device
+    for net in nets:
+        if not (net.executor == "c" and net.use_graph and net.cfg.feature_channels == feat_grid.shape[1] and next(net.parameters()).device == dev
+                and tuple(feat_grid.shape[2:]) == (net.cfg.grid_size,) * 3):
+            return None
+    with torch.cuda.device(dev):
+        for net in nets:
+            net._prepare(dev)
+        src = feat_grid.detach().to(torch.float32).contiguous()[0]
+        base = (tuple(src.shape), tuple(src.stride()), src.dtype, dev.index, id(cont_network),
+                tuple((net.conv_precision, tuple((id(p), p.data_ptr(), p._version) for p in net._param_list())) for net in nets))
+        graphs = seg_network.__dict__.setdefault("_pair_graphs", {})
+        if graphs.get("base") != base:
+            graphs.clear()
+            graphs.update({"base": base, "first_ptr": None})
+        if graphs.get("failed"):
+            return None
+        ent = graphs.get(src.data_ptr()) or graphs.get("copy")
+        if ent is None:
+            outs = _pair_call(seg_network, cont_network, src)     # eager: weight packing, bounds, function attributes -- and this call's result
+            if graphs["first_ptr"] is None:
+                graphs["first_ptr"] = src.data_ptr()
+                return outs[0][None], outs[1][None]
+            in_place = (graphs["first_ptr"] == src.data_ptr() and "copy" not in graphs and os.environ.get("PIXIE_UNET_GRAPH_INPLACE", "1") == "1")
+            try:
+                static_in = src if in_place else src.clone()
+                side = torch.cuda.Stream(dev)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):          # capture must not run on the legacy default stream
+                    _pair_call(seg_network, cont_network, static_in)
+                torch.cuda.current_stream().wait_stream(side)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    static_outs = _pair_call(seg_network, cont_network, static_in)
+            except RuntimeError as exc:                # same kernels either way: the two networks' own routes from here on, loudly
+                warnings.warn(f"pixie_amd: HIP-graph capture of the paired U-Net forward failed ({exc}); continuing with one graph per network",
+                              RuntimeWarning)
+                graphs["failed"] = True
+                return outs[0][None], outs[1][None]
+            ent = (graph, None if in_place else static_in, static_outs)
+            graphs[src.data_ptr() if in_place else "copy"] = ent
+        graph, static_in, static_outs = ent
+        if static_in is not None:
+            static_in.copy_(src)
+        graph.replay()
+        return static_outs[0].clone()[None], static_outs[1].clone()[None]
+
+
 @torch.no_grad()
 def predict_material_field(seg_network: SegmentationUNet, cont_network: RegressionUNet, feat_grid: torch.Tensor,
                            dual_stream: Optional[bool] = None):
@@ -916,8 +989,12 @@ def predict_material_field(seg_network: SegmentationUNet, cont_network: Regressi
         cur.wait_stream(s1); cur.wait_stream(s2)
         seg_logits.record_stream(cur); cont_pred.record_stream(cur)
     else:
-        seg_logits = seg_network(feat_grid)
-        cont_pred = cont_network(feat_grid)
+        pair = _forward_pair(seg_network, cont_network, feat_grid)
+        if pair is not None:
+            seg_logits, cont_pred = pair
+        else:
+            seg_logits = seg_network(feat_grid)
+            cont_pred = cont_network(feat_grid)
     ops = seg_network._runner.ops
     combined, seg_pred = [], []
     for n in range(feat_grid.shape[0]):

@@ -1037,6 +1037,96 @@ int pixie_ray_composite_forward(const pixie_ray_desc* desc, const pixie_ray_inpu
 int pixie_ray_composite_backward(const pixie_ray_desc* desc, const pixie_ray_inputs* inputs, const pixie_ray_upstream* upstream,
                                  const pixie_ray_grads* grads, void* d_scratch, void* stream);
 
+/* ---- proposal sampling and its losses (pixie_amd/csrc/ray_sample.hip) ----
+ * nerfstudio's SpacedSampler family and PDFSampler.generate_ray_samples with Frustums.get_positions, and interlevel_loss /
+ * distortion_loss forward and backward.  All arrays are float32, contiguous, on the device; R = n_rays.  The samplers have no
+ * gradient (the reference detaches the bins); the losses are differentiable in the weights alone.  Random numbers and the linspace
+ * tables are inputs.  Limits: 1 <= R <= 2^24, at most 1024 existing and 1024 produced samples per ray (with include_original:
+ * n_samples + n_existing + 1 <= 1024), at most 8 proposal levels.  Anything else is refused with a non-zero return before any
+ * launch.  Every sum has one fixed order: bit-identical from run to run, under a permutation of the rays and for any R.  No
+ * floating-point atomics.  Asynchronous on `stream`: no synchronise, no host read-back. */
+typedef struct pixie_ray_sample_desc {
+    int64_t n_rays;
+    int32_t n_samples;             /* spaced: the samples produced; pdf: num_samples, so n_samples + 1 new bins */
+    int32_t n_existing;            /* pdf: samples of the existing level; spaced: ignored */
+    int32_t spacing;               /* 0 uniform, 1 linear in disparity, 2 sqrt, 3 log, 4 uniform / linear-disparity piecewise;
+                                      pdf only: -1 = a foreign spacing function, the spacing bins are the only output */
+    int32_t jitter_stride;         /* 0: no jitter (eval mode), 1: one per ray (single_jitter), n_samples + 1: one per bin */
+    int32_t include_original;      /* pdf: merge the existing bins into the new ones */
+    float histogram_padding;       /* pdf */
+    float eps;                     /* pdf: the weight an empty ray is padded to */
+    float anneal;                  /* pdf: weights are raised to this power (float(pow(double))); 1 skips it */
+    float u_scale;                 /* pdf: u_k = table_k + jitter * u_scale (torch on the device: float32(1) / (n_samples + 1)) */
+    float u_offset;                /* pdf without jitter: u_k = table_k + u_offset (float32(1 / (2 (n_samples + 1)))) */
+} pixie_ray_sample_desc;
+typedef struct pixie_ray_sample_inputs {
+    const float* d_nears;          /* (R) spaced */
+    const float* d_fars;           /* (R) spaced */
+    const float* d_origins;        /* (R, 3) or NULL: only for positions */
+    const float* d_directions;     /* (R, 3) */
+    const float* d_table;          /* spaced: linspace(0, 1, n_samples + 1); pdf: linspace(0, 1 - 1 / (n_samples + 1), n_samples + 1) */
+    const float* d_jitter;         /* (R, jitter_stride) uniform in [0, 1), or NULL */
+    const float* d_existing_bins;  /* pdf: (R, n_existing + 1) spacing bins, non-decreasing */
+    const float* d_weights;        /* pdf: (R, n_existing) */
+    const float* d_s_near;         /* pdf: (R) spacing_fn(near), the spaced call's output; NULL with a foreign spacing */
+    const float* d_s_far;
+} pixie_ray_sample_inputs;
+/* M = n_samples (spaced, pdf) or n_samples + n_existing + 1 (pdf with include_original).  NULL = not wanted. */
+typedef struct pixie_ray_sample_outputs {
+    float* d_bins;                 /* (R, M + 1) spacing bins */
+    float* d_starts;               /* (R, M) euclidean */
+    float* d_ends;                 /* (R, M) */
+    float* d_deltas;               /* (R, M) ends - starts */
+    float* d_positions;            /* (R, M, 3) origins + directions * (starts + ends) / 2 */
+    float* d_s_near;               /* (R) spaced only */
+    float* d_s_far;
+} pixie_ray_sample_outputs;
+int pixie_ray_sample_spaced(const pixie_ray_sample_desc* desc, const pixie_ray_sample_inputs* inputs, const pixie_ray_sample_outputs* outputs,
+                            void* stream);
+/* A NaN weight makes the ray's cdf all zero: every new bin lands on the ray's last existing edge. */
+int pixie_ray_sample_pdf(const pixie_ray_sample_desc* desc, const pixie_ray_sample_inputs* inputs, const pixie_ray_sample_outputs* outputs,
+                         void* stream);
+
+#define PIXIE_RAY_MAX_LEVELS 8
+/* loss = sum over levels of mean over (R, n_fine) of clip(w - w_outer, 0)^2 / (w + 1e-7); d_loss: one float */
+typedef struct pixie_ray_interlevel_desc {
+    int64_t n_rays;
+    int32_t n_fine;                                /* samples of the last level, whose edges and weights bound the others */
+    int32_t n_levels;                              /* proposal levels, 1 .. 8 */
+    int32_t n_proposal[PIXIE_RAY_MAX_LEVELS];      /* samples per proposal level */
+    int32_t per_sample;                            /* 1: lossfun_outer itself, one level: the forward writes the (R, n_fine) terms and
+                                                      no mean, the backward's d_upstream is (R, n_fine) */
+} pixie_ray_interlevel_desc;
+typedef struct pixie_ray_interlevel_inputs {
+    const float* d_fine_edges;                     /* (R, n_fine + 1) spacing bins */
+    const float* d_fine_weights;                   /* (R, n_fine) */
+    const float* d_edges[PIXIE_RAY_MAX_LEVELS];    /* (R, n_proposal[l] + 1) */
+    const float* d_weights[PIXIE_RAY_MAX_LEVELS];  /* (R, n_proposal[l]) */
+} pixie_ray_interlevel_inputs;
+typedef struct pixie_ray_interlevel_grads {
+    float* d_weights[PIXIE_RAY_MAX_LEVELS];        /* (R, n_proposal[l]), WRITTEN; NULL = not wanted */
+} pixie_ray_interlevel_grads;
+int pixie_ray_interlevel_bytes(const pixie_ray_interlevel_desc* desc, int64_t* scratch_bytes);   /* 4 R n_levels: one float per ray and level */
+int pixie_ray_interlevel_forward(const pixie_ray_interlevel_desc* desc, const pixie_ray_interlevel_inputs* inputs, float* d_loss,
+                                 float* d_per_sample, void* d_scratch, void* stream);
+/* d_upstream: dL/d loss, one float on the device.  The fine level gets no gradient. */
+int pixie_ray_interlevel_backward(const pixie_ray_interlevel_desc* desc, const pixie_ray_interlevel_inputs* inputs, const float* d_upstream,
+                                  const pixie_ray_interlevel_grads* grads, void* stream);
+
+/* loss = mean over rays of sum_i w_i sum_j w_j |u_i - u_j| + sum_i w_i^2 (t_{i+1} - t_i) / 3, u the interval mid-points; the double
+ * sum is direct, S^2 terms per ray from LDS: no (R, S, S) array exists.  d_edges (R, S + 1), d_weights and d_grad_weights (R, S). */
+typedef struct pixie_ray_distortion_desc {
+    int64_t n_rays;
+    int32_t n_samples;
+    int32_t per_ray;               /* backward: 1 = d_upstream is (R), the gradient of lossfun_distortion's per-ray values */
+} pixie_ray_distortion_desc;
+int pixie_ray_distortion_bytes(const pixie_ray_distortion_desc* desc, int64_t* scratch_bytes);   /* 4 R */
+/* d_scratch receives the per-ray values (lossfun_distortion); d_loss their mean, or NULL */
+int pixie_ray_distortion_forward(const pixie_ray_distortion_desc* desc, const float* d_edges, const float* d_weights, float* d_loss,
+                                 void* d_scratch, void* stream);
+int pixie_ray_distortion_backward(const pixie_ray_distortion_desc* desc, const float* d_edges, const float* d_weights, const float* d_upstream,
+                                  float* d_grad_weights, void* stream);
+
 /* ======================================================================================
  * Diagnostic entry points -- NOT part of the drop-in ABI.  They exist only in the -DPIXIE_DIAG build of the same sources,
  * libpixie_hip_diag.so, which the parity tests (per-phase comparison with the oracle) and the profilers (per-launch timings)

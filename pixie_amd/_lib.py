@@ -165,6 +165,49 @@ class RayGrads(C.Structure):
     _fields_ = [("d_densities", C.c_void_p), ("d_weights", C.c_void_p), ("d_rgb", C.c_void_p), ("d_features", C.c_void_p)]
 
 
+RAY_SAMPLE_MAX_SAMPLES, RAY_SAMPLE_MAX_LEVELS = 1024, 8   # csrc/ray_sample_math.h
+
+
+class RaySampleDesc(C.Structure):
+    """struct pixie_ray_sample_desc"""
+    _fields_ = [("n_rays", C.c_int64), ("n_samples", C.c_int32), ("n_existing", C.c_int32), ("spacing", C.c_int32), ("jitter_stride", C.c_int32),
+                ("include_original", C.c_int32), ("histogram_padding", C.c_float), ("eps", C.c_float), ("anneal", C.c_float),
+                ("u_scale", C.c_float), ("u_offset", C.c_float)]
+
+
+class RaySampleInputs(C.Structure):
+    """struct pixie_ray_sample_inputs"""
+    _fields_ = [(name, C.c_void_p) for name in ("d_nears", "d_fars", "d_origins", "d_directions", "d_table", "d_jitter", "d_existing_bins",
+                                                "d_weights", "d_s_near", "d_s_far")]
+
+
+class RaySampleOutputs(C.Structure):
+    """struct pixie_ray_sample_outputs"""
+    _fields_ = [(name, C.c_void_p) for name in ("d_bins", "d_starts", "d_ends", "d_deltas", "d_positions", "d_s_near", "d_s_far")]
+
+
+class RayInterlevelDesc(C.Structure):
+    """struct pixie_ray_interlevel_desc"""
+    _fields_ = [("n_rays", C.c_int64), ("n_fine", C.c_int32), ("n_levels", C.c_int32), ("n_proposal", C.c_int32 * RAY_SAMPLE_MAX_LEVELS),
+                ("per_sample", C.c_int32)]
+
+
+class RayInterlevelInputs(C.Structure):
+    """struct pixie_ray_interlevel_inputs"""
+    _fields_ = [("d_fine_edges", C.c_void_p), ("d_fine_weights", C.c_void_p), ("d_edges", C.c_void_p * RAY_SAMPLE_MAX_LEVELS),
+                ("d_weights", C.c_void_p * RAY_SAMPLE_MAX_LEVELS)]
+
+
+class RayInterlevelGrads(C.Structure):
+    """struct pixie_ray_interlevel_grads"""
+    _fields_ = [("d_weights", C.c_void_p * RAY_SAMPLE_MAX_LEVELS)]
+
+
+class RayDistortionDesc(C.Structure):
+    """struct pixie_ray_distortion_desc"""
+    _fields_ = [("n_rays", C.c_int64), ("n_samples", C.c_int32), ("per_ray", C.c_int32)]
+
+
 class FieldVoxelizeDesc(C.Structure):
     """struct pixie_field_voxelize_desc"""
     _fields_ = [("density", HashMlpDesc), ("color", HashMlpDesc), ("feature", HashMlpDesc),
@@ -365,6 +408,14 @@ SIGNATURES = {
     "pixie_ray_composite_bytes": (_I, [C.POINTER(RayDesc), C.POINTER(_I64)]),
     "pixie_ray_composite_forward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayOutputs), _VP]),
     "pixie_ray_composite_backward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayUpstream), C.POINTER(RayGrads), _VP, _VP]),
+    "pixie_ray_sample_spaced": (_I, [C.POINTER(RaySampleDesc), C.POINTER(RaySampleInputs), C.POINTER(RaySampleOutputs), _VP]),
+    "pixie_ray_sample_pdf": (_I, [C.POINTER(RaySampleDesc), C.POINTER(RaySampleInputs), C.POINTER(RaySampleOutputs), _VP]),
+    "pixie_ray_interlevel_bytes": (_I, [C.POINTER(RayInterlevelDesc), C.POINTER(_I64)]),
+    "pixie_ray_interlevel_forward": (_I, [C.POINTER(RayInterlevelDesc), C.POINTER(RayInterlevelInputs), _VP, _VP, _VP, _VP]),
+    "pixie_ray_interlevel_backward": (_I, [C.POINTER(RayInterlevelDesc), C.POINTER(RayInterlevelInputs), _VP, C.POINTER(RayInterlevelGrads), _VP]),
+    "pixie_ray_distortion_bytes": (_I, [C.POINTER(RayDistortionDesc), C.POINTER(_I64)]),
+    "pixie_ray_distortion_forward": (_I, [C.POINTER(RayDistortionDesc), _VP, _VP, _VP, _VP, _VP]),
+    "pixie_ray_distortion_backward": (_I, [C.POINTER(RayDistortionDesc), _VP, _VP, _VP, _VP, _VP]),
     "pixie_field_voxelize": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pixie_field_query_points": (_I, [C.POINTER(FieldVoxelizeDesc), _VP, _I64, _D, _VP, _VP, _VP, _VP, _VP]),
 }

@@ -10,7 +10,7 @@ C-wide feature (f3rm/renderer.py) from them.  Here that span is one autograd.Fun
                                                                      with the weights given
 
 Differentiable: densities, rgb, features, and (for the renderers) the weights; `weights` is itself an output of composite that takes
-a gradient, which is how torch's distortion and interlevel losses reach the densities.  Not differentiable: deltas, starts, ends (the
+a gradient, which is how the distortion and interlevel losses (pixie_amd.ray_sampling) reach the densities.  Not differentiable: deltas, starts, ends (the
 reference detaches the bins), the median depth, and the backward itself.  Deviations from torch's autograd on the same lines
 (INTEGRATION 1a row 26): sums run in one fixed order, so results are bit-identical from run to run and under a permutation of the
 rays; on a ray with a NaN density the weights from that sample onward are 0 as in the reference, and the gradients, which torch makes

@@ -939,6 +939,55 @@ int pixie_hashmlp_forward_saved(const pixie_hashmlp_desc* desc, const float* d_p
 int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, const float* d_out,
                            const void* d_saved, const float* d_dout, const pixie_hashmlp_grads* grads, void* d_scratch, void* stream);
 
+/* ---- proposal density field: hash grid -> 16-wide MLP -> trunc_exp, fused (pixie_amd/csrc/density_field.hip) ----
+ * nerfstudio's HashMLPDensityField.get_density (fields/density_fields.py:94-117), from nerf-frame sample positions to densities, in
+ * one launch; what ProposalNetworkSampler calls once per proposal level.  Per point, float32, unfused up to the cell (hashgrid_math.h):
+ *     p = world_to_nerf x (if given);  contraction ? L-infinity contraction then (p + 2) / 4 : (p - aabb_lo) / (aabb_hi - aabb_lo)
+ *     selector = all of 0 < p < 1;  the grid sees p * selector;  per level the trilinear blend of 8 table rows
+ *     z_j = fmaf chain over the inputs in index order from b_j (or 0), ReLU, hidden width exactly 16, n_hidden hidden layers
+ *     density = average_init_density * exp(h) * selector
+ * A point whose selector is 0 (on or outside a face, p exactly 0, any NaN coordinate) gets density exactly 0, contributes nothing to any
+ * gradient and issues no table atomic; its d_raw is the network's output at p = 0. */
+#define PIXIE_DENSITY_FIELD_WIDTH 16
+#define PIXIE_DENSITY_FIELD_MAX_LAYERS 3     /* up to 2 hidden layers + the output layer */
+#define PIXIE_DENSITY_FIELD_MAX_INPUT 64     /* n_levels * features_per_level */
+typedef struct pixie_density_field_desc {
+    int32_t n_levels;              /* 1 .. 16 */
+    int32_t features_per_level;    /* 2, 4 or 8 */
+    int32_t n_hidden;              /* 0 (one linear layer: the reference's use_linear), 1 or 2 */
+    int32_t hidden_width;          /* must be 16 */
+    int32_t contraction;           /* 1: L-infinity scene contraction, then (p + 2) / 4;  0: the aabb */
+    float average_init_density;
+    pixie_hashgrid_level level[PIXIE_HASHMLP_MAX_LEVELS];
+    const float* d_table;          /* (table_rows, features_per_level) float32, 16-byte aligned */
+    int64_t table_rows;
+    const float* d_weight[PIXIE_DENSITY_FIELD_MAX_LAYERS];   /* layer i of n_hidden + 1: (out_i, in_i) row-major float32 */
+    const float* d_bias[PIXIE_DENSITY_FIELD_MAX_LAYERS];     /* NULL (no bias) or (out_i) float32 */
+    const float* d_world_to_nerf;  /* NULL (identity) or 12 float32 on the device: 3 x 4 row-major */
+    float aabb[6];                 /* lo[3], hi[3]; read when contraction == 0, hi > lo */
+} pixie_density_field_desc;
+typedef struct pixie_density_field_grads {   /* any pointer may be NULL: that gradient is not wanted */
+    float* d_table;                           /* (table_rows, F) */
+    float* d_weight[PIXIE_DENSITY_FIELD_MAX_LAYERS];
+    float* d_bias[PIXIE_DENSITY_FIELD_MAX_LAYERS];
+} pixie_density_field_grads;
+/* saved_bytes is 0: the backward recomputes the forward from the positions.  scratch_bytes, for a 256-byte aligned d_scratch:
+ *     [0, 256)     header: uint32 bits of M = max |dX_grid|, int32 shift s, int32 state (0 scattered, 1 M == 0, 2 M not finite)
+ *     then, each rounded up to 256 bytes: masked unit positions 4 (3 n) | dX of the grid columns 4 (in_dim n) |
+ *     slab partials 4 slabs params | the table's accumulators 8 table_rows F,
+ *     slabs = clamp(ceil(n / 256), 1, 1024), params = every weight and bias of the network (csrc/density_field_math.h). */
+int pixie_density_field_train_bytes(const pixie_density_field_desc* desc, int64_t n, int64_t* saved_bytes, int64_t* scratch_bytes);
+/* d_positions (n, 3) float32 -> d_density (n) float32 and, unless NULL, d_raw (n) = h.  One launch; nothing is saved for the backward.
+ * Bit-identical from run to run, for a point alone or inside a batch, and under a permutation of the points. */
+int pixie_density_field_forward(const pixie_density_field_desc* desc, const float* d_positions, int64_t n, float* d_density, float* d_raw,
+                                void* stream);
+/* d_ddensity (n) = dL/d density.  WRITES (does not accumulate) every gradient whose pointer is not NULL; positions get no gradient.
+ * The table gradient is the 64-bit fixed-point scatter of csrc/hashgrid_grad_math.h: bit-identical from run to run and under a
+ * permutation; a non-finite dX makes the WHOLE table gradient NaN.  Weight and bias gradients: one partial per slab, summed in slab
+ * order: bit-identical from run to run.  No floating-point atomics.  Refusals: the limits above, n > 2^24.  Asynchronous on `stream`. */
+int pixie_density_field_backward(const pixie_density_field_desc* desc, const float* d_positions, int64_t n, const float* d_ddensity,
+                                 const pixie_density_field_grads* grads, void* d_scratch, void* stream);
+
 typedef struct pixie_field_voxelize_desc {
     pixie_hashmlp_desc density;    /* out_dim = 1 + G <= 63, out_activation 0: column 0 the log density, columns 1.. the geometry
                                     * features (nerfacto_field.py:203-232) */

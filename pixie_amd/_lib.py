@@ -134,6 +134,24 @@ class HashMlpGrads(C.Structure):
                 ("d_extra", C.c_void_p)]
 
 
+DENSITY_FIELD_WIDTH, DENSITY_FIELD_MAX_LAYERS, DENSITY_FIELD_MAX_INPUT = 16, 3, 64   # PIXIE_DENSITY_FIELD_*
+
+
+class DensityFieldDesc(C.Structure):
+    """struct pixie_density_field_desc"""
+    _fields_ = [("n_levels", C.c_int32), ("features_per_level", C.c_int32), ("n_hidden", C.c_int32), ("hidden_width", C.c_int32),
+                ("contraction", C.c_int32), ("average_init_density", C.c_float),
+                ("level", HashGridLevel * HASHMLP_MAX_LEVELS),
+                ("d_table", C.c_void_p), ("table_rows", C.c_int64),
+                ("d_weight", C.c_void_p * DENSITY_FIELD_MAX_LAYERS), ("d_bias", C.c_void_p * DENSITY_FIELD_MAX_LAYERS),
+                ("d_world_to_nerf", C.c_void_p), ("aabb", C.c_float * 6)]
+
+
+class DensityFieldGrads(C.Structure):
+    """struct pixie_density_field_grads"""
+    _fields_ = [("d_table", C.c_void_p), ("d_weight", C.c_void_p * DENSITY_FIELD_MAX_LAYERS), ("d_bias", C.c_void_p * DENSITY_FIELD_MAX_LAYERS)]
+
+
 RAY_MAX_SAMPLES, RAY_MAX_FEATURE_SAMPLES, RAY_MAX_CHANNELS, RAY_MAX_RAYS = 1024, 256, 2048, 1 << 24   # csrc/ray_render_math.h
 
 
@@ -405,6 +423,9 @@ SIGNATURES = {
     "pixie_hashmlp_train_bytes": (_I, [C.POINTER(HashMlpDesc), _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "pixie_hashmlp_forward_saved": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP]),
     "pixie_hashmlp_backward": (_I, [C.POINTER(HashMlpDesc), _VP, _VP, _I64, _VP, _VP, _VP, C.POINTER(HashMlpGrads), _VP, _VP]),
+    "pixie_density_field_train_bytes": (_I, [C.POINTER(DensityFieldDesc), _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "pixie_density_field_forward": (_I, [C.POINTER(DensityFieldDesc), _VP, _I64, _VP, _VP, _VP]),
+    "pixie_density_field_backward": (_I, [C.POINTER(DensityFieldDesc), _VP, _I64, _VP, C.POINTER(DensityFieldGrads), _VP, _VP]),
     "pixie_ray_composite_bytes": (_I, [C.POINTER(RayDesc), C.POINTER(_I64)]),
     "pixie_ray_composite_forward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayOutputs), _VP]),
     "pixie_ray_composite_backward": (_I, [C.POINTER(RayDesc), C.POINTER(RayInputs), C.POINTER(RayUpstream), C.POINTER(RayGrads), _VP, _VP]),

@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpixie_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpixie_hip_diag.so")   # same sources + -DPIXIE_DIAG (tests, profilers)
 ARCH = "gfx950"
-SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip", "occupancy.hip", "part_segmentation.hip", "field_query.hip", "field_query_backward.hip", "ray_render.hip", "ray_sample.hip"]
+SOURCES = ["common.hip", "mpm.hip", "unet_ops.hip", "conv3d_mfma.hip", "conv3d_f16x3.hip", "unet_exec.hip", "projector_fused.hip", "field_transfer.hip", "particle_filling.hip", "raster.hip", "raster_backward.hip", "scene_ingest.hip", "knn.hip", "photometric.hip", "gs_optim.hip", "occupancy.hip", "part_segmentation.hip", "field_query.hip", "field_query_backward.hip", "ray_render.hip", "ray_sample.hip", "density_field.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
 # Per-file flags.  mpm.hip: hipcc's SLP vectoriser turns a third of the fused MPM kernel's fp32 arithmetic into packed
@@ -51,11 +51,13 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 # g++ rounds the header (its exp is a double exp rounded once on both sides); the feature kernels move 4 bytes per multiply-add, so the unfused arithmetic is not what bounds them.
 # ray_sample.hip: the same, for ray_sample_math.h and tests/test_ray_sampling_math.py: stratified bins, spacing maps, deltas, positions and
 # the cdf interpolation round as float32 NumPy does, so a level's bins are bit-equal to torch's on the same random numbers.
+# density_field.hip: the same, for hashgrid_math.h (front end, cells, corner weights: the forward and the scatter land on the same rows)
+# and density_field_math.h; the layers are explicit fmaf, which the flag leaves alone.
 EXTRA_FLAGS = {"mpm.hip": ["-fno-slp-vectorize"], "raster.hip": ["-ffp-contract=off"], "raster_backward.hip": ["-ffp-contract=off"],
                "scene_ingest.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "gs_optim.hip": ["-ffp-contract=off"],
                "occupancy.hip": ["-ffp-contract=off"], "part_segmentation.hip": ["-ffp-contract=off"], "field_query.hip": ["-ffp-contract=off"],
                "field_query_backward.hip": ["-ffp-contract=off"], "ray_render.hip": ["-ffp-contract=off"],
-               "ray_sample.hip": ["-ffp-contract=off"]}
+               "ray_sample.hip": ["-ffp-contract=off"], "density_field.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

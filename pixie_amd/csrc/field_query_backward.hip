@@ -18,6 +18,7 @@
 // Built with -ffp-contract=off like field_query.hip: cells and corner weights round as the forward's.
 #include "field_query_body.h"
 #include "hashgrid_grad_math.h"
+#include "hashgrid_table_grad.h"
 
 namespace {
 
@@ -319,37 +320,12 @@ __global__ void slab_sum_kernel(const float* part, const float* bpart, int slabs
 }
 
 // ---- table gradient -----------------------------------------------------------------------------------------------------------
+// hashgrid_table_grad.h's scatter at the unit-cube positions the forward took
 __global__ __launch_bounds__(THREADS) void table_scatter_kernel(const pixie_hashmlp_desc m, const float* d_positions, int64_t n, const float* d_dxg,
                                                                 const unsigned int* d_header, unsigned long long* d_acc) {
-    const unsigned int bits = d_header[0];
-    if (hgg::state_of(bits) != hgg::kNormal) return;
-    const int s = hgg::shift_of(bits, n);
-    const int F = m.features_per_level, per = 8 * F;
-    const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-    if (t >= n * m.n_levels * per) return;
-    const int f = (int)(t % F), k = (int)((t / F) % 8);
-    const int64_t pl = t / per, point = pl % n;
-    const int l = (int)(pl / n);
-    hg::Level lv;
-    lv.scale = m.level[l].scale; lv.shift = m.level[l].shift; lv.res = m.level[l].res;
-    lv.size = m.level[l].size; lv.offset = m.level[l].offset; lv.dense = m.level[l].dense;
-    const float pp[3] = {d_positions[3 * point], d_positions[3 * point + 1], d_positions[3 * point + 2]};
-    const hg::Cell cell = hg::cell_of(lv, pp);
-    const float c = hg::corner_weight(cell, k) * d_dxg[(int64_t)(l * F + f) * n + point];
-    const long long q = hgg::quantise(c, s);
-    if (q != 0) atomicAdd(d_acc + (size_t)hg::corner_row_k(lv, cell, k) * F + f, (unsigned long long)q);
-}
-
-// d_table[i] = float32(double(acc[i]) 2^-s), NaN everywhere if the maximum was not finite; the header receives s and the state
-__global__ void table_finalise_kernel(const long long* d_acc, int64_t count, int64_t n, unsigned int* d_header, float* d_table) {
-    const unsigned int bits = d_header[0];
-    const int state = hgg::state_of(bits), s = state == hgg::kNormal ? hgg::shift_of(bits, n) : 0;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        reinterpret_cast<int*>(d_header)[1] = s;
-        reinterpret_cast<int*>(d_header)[2] = state;
-    }
-    if (i < count) d_table[i] = state == hgg::kNonFinite ? __int_as_float(0x7fc00000) : hgg::finalise(d_acc[i], s);
+    table_scatter_item(m, [d_positions](int64_t point, float* pp) {
+        pp[0] = d_positions[3 * point]; pp[1] = d_positions[3 * point + 1]; pp[2] = d_positions[3 * point + 2];
+    }, n, d_dxg, d_header, d_acc, THREADS);
 }
 
 int check_call(const pixie_hashmlp_desc* desc, const float* d_positions, const float* d_extra, int64_t n, const char* what) {

@@ -241,15 +241,17 @@ def fold_color_head(weights, biases, n_direction: int, n_geo: int, direction_enc
     return [w0[:, n_direction:n_direction + n_geo].astype(np.float32)] + list(weights[1:]), [b0.astype(np.float32)] + rest
 
 
-def split_tcnn_params(params, in_dim: int, n_hidden: int, out_dim: int, table_rows: int = 0, features_per_level: int = 0, pad_value: float = 1.0):
+def split_tcnn_params(params, in_dim: int, n_hidden: int, out_dim: int, table_rows: int = 0, features_per_level: int = 0, pad_value: float = 1.0,
+                      width: int = WIDTH):
     """The flat `params` vector of a tiny-cuda-nn FullyFusedMLP (+ grid) in the published layout: network weights first, then the
     grid; each layer (out, in) row-major without bias; the first layer's `in` and the last layer's `out` padded to multiples of 16;
-    the padding input columns hold `pad_value` (1.0), so their weights sum into a bias.  Refuses unless the count this implies
+    the padding input columns hold `pad_value` (1.0), so their weights sum into a bias.  `width`: the hidden layers' width (64; 16 for
+    the proposal density fields).  Refuses unless the count this implies
     equals params.numel() exactly.  Returns (weights, biases, table or None)."""
     p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
     p = p.reshape(-1).astype(np.float32)
     in_pad, out_pad = (in_dim + 15) // 16 * 16, (out_dim + 15) // 16 * 16
-    shapes = [(WIDTH, in_pad)] + [(WIDTH, WIDTH)] * (n_hidden - 1) + [(out_pad, WIDTH)]
+    shapes = [(width, in_pad)] + [(width, width)] * (n_hidden - 1) + [(out_pad, width)]
     expect = sum(a * b for a, b in shapes) + table_rows * features_per_level
     if p.size != expect:
         raise ValueError(f"split_tcnn_params: the layout implies {expect} parameters ({shapes} + {table_rows} x {features_per_level} grid), "

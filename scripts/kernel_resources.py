@@ -10,5 +10,5 @@ for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     def g(k):
         m = re.search(k + r": (\d+)", b)
         return m.group(1) if m else "?"
-    print(name[:64], "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "spill", g("VGPRs Spill"), "scratch", g(r"ScratchSize \[bytes/lane\]"),
+    print(name[:64], "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "spill", g("VGPRs Spill"), "SGPR-spill", g("SGPRs Spill"), "scratch", g(r"ScratchSize \[bytes/lane\]"),
           "SGPR", g("TotalSGPRs"), "occ", g(r"Occupancy \[waves/SIMD\]"), "LDS", g(r"LDS Size \[bytes/block\]"))

@@ -13,6 +13,7 @@
 #include "../../include/pixie_hip.h"
 #include "common.h"
 #include "launch_record.h"
+#include "unet_ops_internal.h"
 
 namespace pixie {
 

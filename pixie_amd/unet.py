@@ -118,7 +118,7 @@ def fill_conv_desc(lib, alloc, parts: Sequence[torch.Tensor], packed_w, bias, co
 
 class PendingStats:
     """Partial channel statistics a convolution left behind (pixie_conv_desc.d_out_stats) and that nothing has added up yet;
-    HipOps.stats_norm_finalize does, in the launch that also makes the consumer's affine (unet_exec.hip: Tens::partials_off)."""
+    HipOps.stats_norm_finalize does, in the launch that also makes the consumer's affine (unet_walk.h: Tens::partials_off)."""
 
     def __init__(self, stats: torch.Tensor, desc: ConvDesc, cout: int):
         self.stats, self.desc, self.cout = stats, desc, cout
@@ -397,7 +397,7 @@ class UNetRunner:
         return cache[k]
 
     def _norm(self, cache: dict, parts: List[torch.Tensor], spatial: int, mode: int, groups: int = 1, weight=None, bias=None):
-        """The prologue affine of a normalisation over th.cat(parts), from the tensors' statistics (unet_exec.hip:
+        """The prologue affine of a normalisation over th.cat(parts), from the tensors' statistics (unet_walk.h:
         Exec::norm_finalize).  One launch: partial statistics a producer left behind are added up in it."""
         ops = self.ops
         for t in parts:
@@ -439,7 +439,7 @@ class UNetRunner:
             kw["out_size"] = out_size
         if skip is not None:
             kw["skip"] = skip
-        # (unet_exec.hip: Exec::conv takes the same decision; injected reference operators keep the 27-tap form)
+        # (unet_walk.h: Exec::conv takes the same decision; injected reference operators keep the 27-tap form)
         sub = self.subpixel and upsample and ksize == 3 and stride == 1 and hasattr(ops, "pack_conv_subpixel")
         if sub:
             kw["subpixel"] = True

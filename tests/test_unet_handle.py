@@ -72,6 +72,29 @@ def test_workspace_sizing_is_a_dry_run():
     lib.pixie_unet_destroy(h16); lib.pixie_unet_destroy(h32)
 
 
+# pixie_unet_workspace_bytes(d, d, d) per configuration: (f16x3, exact fp32), recorded from a CPU build of the commit before the
+# handle's source was split by concern (unet_plan.h, workspace_arena.h, unet_walk.h)
+WORKSPACE_BYTES = {
+    "baseline_config2_128": (4_297_105_920, 4_563_578_368),
+    "shipped_64x768": (537_174_528, 570_600_960),
+    "odd9_attention": (290_560, 338_176),
+    "light_projector": (233_216, 238_592),
+}
+
+
+@pytest.mark.parametrize("precision", [0, 1])
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_workspace_bytes_are_pinned(name, precision):
+    """First fit makes the peak depend on the order of every allocation and release of the plan walk: a reordered walk, a changed
+    rounding or head layout moves these numbers without a GPU."""
+    cfg = CONFIGS[name]
+    lib, h, rc = _create(cfg, precision)
+    assert rc == 0, lib.pixie_last_error()
+    d = cfg.grid_size
+    assert lib.pixie_unet_workspace_bytes(h, d, d, d) == WORKSPACE_BYTES[name][precision]
+    lib.pixie_unet_destroy(h)
+
+
 def test_bad_configurations_are_rejected():
     lib, h, rc = _create(UNetConfig(64, 32, 64, 3, (), (), 16, 8))
     assert rc != 0 and b"channel_mult" in lib.pixie_last_error()

@@ -24,6 +24,7 @@
 #include "../../include/pixie_hip.h"
 #include "common.h"
 #include "density_field_math.h"
+#include "hashgrid_check.h"
 #include "hashgrid_grad_math.h"
 #include "hashgrid_math.h"
 #include "hashgrid_table_grad.h"
@@ -74,11 +75,7 @@ __device__ inline void stage_weights(const pixie_density_field_desc& m, int in_d
 // nerf-frame (or world) position -> masked unit position; returns the selector
 __device__ inline int front_end(const pixie_density_field_desc& m, const float* A, const float* src, float* p) {
     const float x[3] = {src[0], src[1], src[2]};
-    if (A != nullptr) hg::affine(A, x, p);
-    else { p[0] = x[0]; p[1] = x[1]; p[2] = x[2]; }
-    if (m.contraction) hg::contract_linf(p);
-    else hg::normalise_aabb(m.aabb, p);
-    const int sel = hg::selector(p);
+    const int sel = hg::unit_position(A, m.contraction, m.aabb, x, p);
     if (!sel) { p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; }
     return sel;
 }
@@ -96,9 +93,7 @@ __device__ inline float eval_point(const pixie_density_field_desc& m, const NetL
     float h = s.bo;
     if (NH > 0) df::layer_seed(s.b0, acc);
     for (int l = 0; l < m.n_levels; ++l) {
-        hg::Level lv;
-        lv.scale = m.level[l].scale; lv.shift = m.level[l].shift; lv.res = m.level[l].res;
-        lv.size = m.level[l].size; lv.offset = m.level[l].offset; lv.dense = m.level[l].dense;
+        const hg::Level lv = hg::level_of(m.level[l]);
         const hg::Cell c = hg::cell_of(lv, p);
         float v[8][F];
 #pragma unroll
@@ -391,13 +386,7 @@ int check_desc(const pixie_density_field_desc* m, int64_t n, const char* what) {
     PX_REQUIRE(host_in_dim(*m) <= PIXIE_DENSITY_FIELD_MAX_INPUT, "%s: input row of %d columns, at most %d", what, host_in_dim(*m),
                PIXIE_DENSITY_FIELD_MAX_INPUT);
     PX_REQUIRE(m->n_hidden >= 0 && m->n_hidden <= df::kMaxHidden, "%s: %d hidden layers outside 0..%d", what, m->n_hidden, df::kMaxHidden);
-    PX_REQUIRE(m->d_table != nullptr && (reinterpret_cast<uintptr_t>(m->d_table) & 15) == 0, "%s: d_table is null or not 16-byte aligned", what);
-    for (int l = 0; l < m->n_levels; ++l) {
-        const pixie_hashgrid_level& lv = m->level[l];
-        PX_REQUIRE(lv.size > 0 && (int64_t)lv.offset + (int64_t)lv.size <= m->table_rows,
-                   "%s: level %d (offset %u, size %u) does not fit the table of %lld rows", what, l, lv.offset, lv.size, (long long)m->table_rows);
-        PX_REQUIRE(std::isfinite(lv.scale) && std::isfinite(lv.shift), "%s: level %d has a non-finite scale or shift", what, l);
-    }
+    if (check_grid_table(*m, what)) return 1;
     for (int i = 0; i <= m->n_hidden; ++i) PX_REQUIRE(m->d_weight[i] != nullptr, "%s: d_weight[%d] is null", what, i);
     if (!m->contraction)
         for (int a = 0; a < 3; ++a)
@@ -468,15 +457,8 @@ int pixie_density_field_backward(const pixie_density_field_desc* desc, const flo
     for (int i = 0; i <= NH; ++i) any_layer = any_layer || grads->d_weight[i] != nullptr || grads->d_bias[i] != nullptr;
     if (!any_layer && grads->d_table == nullptr) return 0;
     hipStream_t st = as_stream(stream);
-    if (n == 0) {                                 // the empty sum
-        if (grads->d_table != nullptr) PX_CHECK_HIP(hipMemsetAsync(grads->d_table, 0, 4 * (size_t)m.table_rows * F, st));
-        for (int i = 0; i <= NH; ++i) {
-            if (grads->d_weight[i] != nullptr)
-                PX_CHECK_HIP(hipMemsetAsync(grads->d_weight[i], 0, 4 * (size_t)df::layer_out(NH, i) * df::layer_in(in_dim, i), st));
-            if (grads->d_bias[i] != nullptr) PX_CHECK_HIP(hipMemsetAsync(grads->d_bias[i], 0, 4 * (size_t)df::layer_out(NH, i), st));
-        }
-        return 0;
-    }
+    if (n == 0)
+        return zero_empty_grads(*grads, NH + 1, (size_t)m.table_rows * F, [=](int i) { return std::make_pair(df::layer_out(NH, i), df::layer_in(in_dim, i)); }, st);
     PX_REQUIRE(d_positions != nullptr && d_ddensity != nullptr, "%s: d_positions or d_ddensity is null", what);
     PX_REQUIRE(d_scratch != nullptr && (reinterpret_cast<uintptr_t>(d_scratch) & 255) == 0, "%s: d_scratch is null or not 256-byte aligned", what);
     const df::Scratch L = df::scratch_layout(n, in_dim, NH, m.table_rows, F);
@@ -500,15 +482,7 @@ int pixie_density_field_backward(const pixie_density_field_desc* desc, const flo
         hipLaunchKernelGGL(density_slab_sum_kernel, dim3((unsigned)cdiv(pc, 64)), dim3(64), 0, st, (const float*)part, slabs, in_dim, NH, *grads);
         PX_CHECK_HIP(hipGetLastError());
     }
-    if (table) {
-        const int64_t items = n * m.n_levels * 8 * F, count = m.table_rows * F;
-        hipLaunchKernelGGL(density_table_scatter_kernel, dim3((unsigned)((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, m, (const float*)pos, n,
-                           (const float*)dxg, (const unsigned int*)header, acc);
-        PX_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(table_finalise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const long long*)acc, count, n, header,
-                           grads->d_table);
-        PX_CHECK_HIP(hipGetLastError());
-    }
+    if (table) return finish_table_grad(density_table_scatter_kernel, THREADS, m, pos, n, dxg, header, acc, grads->d_table, st);
     return 0;
 }
 

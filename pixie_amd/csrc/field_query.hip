@@ -28,14 +28,9 @@ __global__ __launch_bounds__(THREADS) void hashmlp_forward_kernel(const pixie_ha
     extern __shared__ float lds[];
     float *X = lds + X_OFF, *H = lds + H_OFF, *wl = lds + WL_OFF, *pos = lds + POS_OFF;
     const int64_t tile0 = (int64_t)blockIdx.x * P;
-    const int tid = threadIdx.x;
-    if (tid < 3 * P) {
-        const int p = tid / 3, a = tid - 3 * p;
-        pos[a * P + p] = (d_positions != nullptr && tile0 + p < n) ? d_positions[(tile0 + p) * 3 + a] : 0.f;
-    }
-    __syncthreads();
+    load_tile_positions(d_positions, tile0, n, pos);
     encode_tile(m, pos, d_extra, tile0, n, X);
-    const float* hid = hidden_layers(m, input_width(m), X, X, H, wl);
+    const float* hid = hidden_layers(m, hg::input_width(m), X, X, H, wl);
     output_layer<false>(m, hid, X, wl, nullptr, d_out, tile0, n);
 }
 
@@ -58,6 +53,8 @@ __device__ void tile_positions(const pixie_field_voxelize_desc& v, const float* 
                 x[1] = v.d_axis_y != nullptr ? v.d_axis_y[j] : hg::lattice_coord(v.min_bounds[1], v.voxel_size, j);
                 x[2] = v.d_axis_z != nullptr ? v.d_axis_z[k] : hg::lattice_coord(v.min_bounds[2], v.voxel_size, k);
             }
+            // hg::unit_position, written out: through the call the compiler schedules these kernels differently (same registers), and
+            // scripts/device_code_identity.py against the parent is the bar for this family's helpers
             hg::affine(v.world_to_nerf, x, q);
             if (v.contraction) hg::contract_linf(q); else hg::normalise_aabb(v.aabb, q);
             sel = hg::selector(q);
@@ -79,7 +76,7 @@ __global__ __launch_bounds__(THREADS) void field_density_color_kernel(const pixi
     tile_positions(v, d_points, tile0, n, true, pos, aux);
     __syncthreads();
     encode_tile(v.density, pos, nullptr, tile0, n, X);
-    const float* hid = hidden_layers(v.density, input_width(v.density), X, X, H, wl);
+    const float* hid = hidden_layers(v.density, hg::input_width(v.density), X, X, H, wl);
     float* geo = (hid >= H && hid < H + 64 * P) ? X : H;         // [h_0 | geometry columns | zero rows][P]
     const int last = v.density.n_hidden;
     lds_layer(v.density.d_weight[last], v.density.d_bias[last], v.density.out_dim, 64, false, hid, geo, wl);
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(THREADS) void field_feature_kernel(const pixie_fiel
     if (p < P) aux[p] = (d_scratch != nullptr && tile0 + p < n) ? d_scratch[tile0 + p] : 1.f;
     __syncthreads();
     encode_tile(v.feature, pos, nullptr, tile0, n, X);
-    const float* hid = hidden_layers(v.feature, input_width(v.feature), X, X, H, wl);
+    const float* hid = hidden_layers(v.feature, hg::input_width(v.feature), X, X, H, wl);
     output_layer<HALF>(v.feature, hid, X, wl, aux, d_features, tile0, n);
 }
 

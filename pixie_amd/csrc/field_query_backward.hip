@@ -19,47 +19,11 @@
 #include "field_query_body.h"
 #include "hashgrid_grad_math.h"
 #include "hashgrid_table_grad.h"
+#include "hashmlp_plan.h"
 
 namespace {
 
 constexpr int ZLD = 65;                          // row pitch of the staged gradient chunk [row][point or column]
-constexpr int HEADER_BYTES = 256;
-constexpr int MAX_SLABS = 256, TARGET_BLOCKS = 1024;
-
-inline int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
-inline int host_input_width(const pixie_hashmlp_desc& m) { return m.n_levels * m.features_per_level + 6 * m.n_frequencies + m.n_extra; }
-inline int layer_out(const pixie_hashmlp_desc& m, int i) { return i == m.n_hidden ? m.out_dim : 64; }
-inline int layer_in(const pixie_hashmlp_desc& m, int i) { return i == 0 ? host_input_width(m) : 64; }
-
-// how many slabs of points the weight gradient of an (out, in) layer is cut into: a pure function of n and the shape
-inline int slab_count(int64_t n, int out, int in) {
-    const int64_t tiles = (n + P - 1) / P;
-    int64_t s = TARGET_BLOCKS / ((int64_t)((out + 63) / 64) * ((in + 63) / 64));
-    if (s > MAX_SLABS) s = MAX_SLABS;
-    if (s > tiles) s = tiles;
-    return s < 1 ? 1 : (int)s;
-}
-
-struct ScratchLayout {
-    int64_t dz, dxg, part, acc, total, saved;
-};
-
-ScratchLayout scratch_layout(const pixie_hashmlp_desc& m, int64_t n) {
-    ScratchLayout L;
-    const int F = m.n_levels > 0 ? m.features_per_level : 0;
-    L.dz = HEADER_BYTES;
-    L.dxg = L.dz + round256(4 * (int64_t)64 * m.n_hidden * n);
-    L.part = L.dxg + round256(4 * (int64_t)m.n_levels * F * n);
-    int64_t floats = 0;
-    for (int i = 0; i <= m.n_hidden; ++i) {
-        const int64_t o = layer_out(m, i), k = layer_in(m, i), f = (int64_t)slab_count(n, (int)o, (int)k) * (o * k + o);
-        if (f > floats) floats = f;
-    }
-    L.acc = L.part + round256(4 * floats);
-    L.total = L.acc + round256(8 * m.table_rows * F);
-    L.saved = 4 * n * ((int64_t)host_input_width(m) + 64 * m.n_hidden);
-    return L;
-}
 
 // ---- training forward ---------------------------------------------------------------------------------------------------------
 // rows [rows][P] of LDS -> dst[row][n] at the tile's points
@@ -75,19 +39,15 @@ __global__ __launch_bounds__(THREADS) void hashmlp_forward_saved_kernel(const pi
     extern __shared__ float lds[];
     float *X = lds + X_OFF, *H = lds + H_OFF, *wl = lds + WL_OFF, *pos = lds + POS_OFF;
     const int64_t tile0 = (int64_t)blockIdx.x * P;
-    const int tid = threadIdx.x;
-    if (tid < 3 * P) {
-        const int p = tid / 3, a = tid - 3 * p;
-        pos[a * P + p] = (d_positions != nullptr && tile0 + p < n) ? d_positions[(tile0 + p) * 3 + a] : 0.f;
-    }
-    __syncthreads();
+    load_tile_positions(d_positions, tile0, n, pos);
     encode_tile(m, pos, d_extra, tile0, n, X);
-    const int in_dim = input_width(m);
+    const int in_dim = hg::input_width(m);
     __syncthreads();
     save_rows(X, in_dim, d_saved, tile0, n);
     float* hidden = d_saved + (int64_t)in_dim * n;
     const float* src = X;
-    for (int i = 0; i < m.n_hidden; ++i) {        // hidden_layers(), with the rows leaving after each layer
+    for (int i = 0; i < m.n_hidden; ++i) {        // hidden_layers(), with the rows leaving after each layer (as a per-layer hook of
+                                                  // hidden_layers the same lines compile to other device code)
         float* dst = (src >= H && src < H + 64 * P) ? X : H;
         lds_layer(m.d_weight[i], m.d_bias[i], 64, i == 0 ? in_dim : 64, true, src, dst, wl);
         __syncthreads();
@@ -139,7 +99,7 @@ __global__ __launch_bounds__(THREADS) void hashmlp_backward_kernel(const pixie_h
     __shared__ float wl[64 * WLD];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hi = lane >> 5, mb = wave & 1, nb = wave >> 1;
     const int64_t tile0 = (int64_t)blockIdx.x * P;
-    const int in_dim = input_width(m), out_dim = m.out_dim, act = m.out_activation;
+    const int in_dim = hg::input_width(m), out_dim = m.out_dim, act = m.out_activation;
     const float* hidden = d_saved + (int64_t)in_dim * n;
     const int64_t gp = tile0 + nb * 32 + r;       // the point of this lane's accumulator column
 
@@ -343,9 +303,8 @@ extern "C" {
 int pixie_hashmlp_train_bytes(const pixie_hashmlp_desc* desc, int64_t n, int64_t* saved_bytes, int64_t* scratch_bytes) {
     if (check_desc(desc, "pixie_hashmlp_train_bytes")) return 1;
     PX_REQUIRE(n >= 0 && n <= hgg::kMaxPoints, "pixie_hashmlp_train_bytes: n = %lld outside 0..2^24", (long long)n);
-    const ScratchLayout L = scratch_layout(*desc, n);
-    if (saved_bytes != nullptr) *saved_bytes = L.saved;
-    if (scratch_bytes != nullptr) *scratch_bytes = L.total;
+    if (saved_bytes != nullptr) *saved_bytes = hmp::saved_bytes(*desc, n);
+    if (scratch_bytes != nullptr) *scratch_bytes = hmp::scratch_layout(*desc, n).total;
     return 0;
 }
 
@@ -377,17 +336,11 @@ int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positi
     bool any = grads->d_table != nullptr || grads->d_extra != nullptr;
     for (int i = 0; i <= m.n_hidden; ++i) any = any || grads->d_weight[i] != nullptr || grads->d_bias[i] != nullptr;
     if (!any) return 0;
-    if (n == 0) {                                 // the empty sum
-        if (grads->d_table != nullptr) PX_CHECK_HIP(hipMemsetAsync(grads->d_table, 0, 4 * (size_t)m.table_rows * F, st));
-        for (int i = 0; i <= m.n_hidden; ++i) {
-            if (grads->d_weight[i] != nullptr) PX_CHECK_HIP(hipMemsetAsync(grads->d_weight[i], 0, 4 * (size_t)layer_out(m, i) * layer_in(m, i), st));
-            if (grads->d_bias[i] != nullptr) PX_CHECK_HIP(hipMemsetAsync(grads->d_bias[i], 0, 4 * (size_t)layer_out(m, i), st));
-        }
-        return 0;
-    }
+    if (n == 0)
+        return zero_empty_grads(*grads, m.n_hidden + 1, (size_t)m.table_rows * F, [&m](int i) { return std::make_pair(hmp::layer_out(m, i), hmp::layer_in(m, i)); }, st);
     PX_REQUIRE(d_out != nullptr && d_saved != nullptr && d_dout != nullptr, "%s: d_out, d_saved or d_dout is null", what);
     PX_REQUIRE(d_scratch != nullptr && (reinterpret_cast<uintptr_t>(d_scratch) & 255) == 0, "%s: d_scratch is null or not 256-byte aligned", what);
-    const ScratchLayout L = scratch_layout(m, n);
+    const hmp::ScratchLayout L = hmp::scratch_layout(m, n);
     char* base = reinterpret_cast<char*>(d_scratch);
     unsigned int* header = reinterpret_cast<unsigned int*>(base);
     float* dz = reinterpret_cast<float*>(base + L.dz);
@@ -395,9 +348,9 @@ int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positi
     float* part = reinterpret_cast<float*>(base + L.part);
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(base + L.acc);
     const float* saved = reinterpret_cast<const float*>(d_saved);
-    const int in_dim = host_input_width(m);
+    const int in_dim = hg::input_width(m);
 
-    PX_CHECK_HIP(hipMemsetAsync(header, 0, HEADER_BYTES, st));
+    PX_CHECK_HIP(hipMemsetAsync(header, 0, hmp::kHeaderBytes, st));
     if (grads->d_table != nullptr) PX_CHECK_HIP(hipMemsetAsync(acc, 0, 8 * (size_t)m.table_rows * F, st));
     hipLaunchKernelGGL(hashmlp_backward_kernel, dim3((unsigned)cdiv(n, P)), dim3(THREADS), 0, st, m, n, d_out, d_dout, saved, dz,
                        grads->d_table != nullptr ? dxg : (float*)nullptr, grads->d_extra, header);
@@ -405,9 +358,9 @@ int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positi
 
     for (int i = 0; i <= m.n_hidden; ++i) {
         if (grads->d_weight[i] == nullptr && grads->d_bias[i] == nullptr) continue;
-        const int O = layer_out(m, i), K = layer_in(m, i), k_tiles = (K + 63) / 64, o_tiles = (O + 63) / 64;
-        const int64_t tiles = (n + P - 1) / P, cps = (tiles + slab_count(n, O, K) - 1) / slab_count(n, O, K);
-        const int slabs = (int)((tiles + cps - 1) / cps);
+        const int O = hmp::layer_out(m, i), K = hmp::layer_in(m, i), k_tiles = (K + 63) / 64, o_tiles = (O + 63) / 64;
+        const int slabs = hmp::launched_slabs(n, O, K);
+        const int64_t cps = hmp::chunks_per_slab(n, O, K);
         float* bpart = part + (int64_t)slabs * O * K;
         const float* A = i == 0 ? saved : saved + (int64_t)in_dim * n + (int64_t)(i - 1) * 64 * n;
         const dim3 grid((unsigned)(o_tiles * k_tiles), (unsigned)slabs);
@@ -422,15 +375,7 @@ int pixie_hashmlp_backward(const pixie_hashmlp_desc* desc, const float* d_positi
         PX_CHECK_HIP(hipGetLastError());
     }
 
-    if (grads->d_table != nullptr) {
-        const int64_t items = n * m.n_levels * 8 * F, count = m.table_rows * F;
-        hipLaunchKernelGGL(table_scatter_kernel, dim3((unsigned)((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, m, d_positions, n,
-                           (const float*)dxg, (const unsigned int*)header, acc);
-        PX_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(table_finalise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const long long*)acc, count, n, header,
-                           grads->d_table);
-        PX_CHECK_HIP(hipGetLastError());
-    }
+    if (grads->d_table != nullptr) return finish_table_grad(table_scatter_kernel, THREADS, m, d_positions, n, dxg, header, acc, grads->d_table, st);
     return 0;
 }
 

@@ -11,7 +11,9 @@
 
 #include "../../include/pixie_hip.h"
 #include "common.h"
+#include "hashgrid_check.h"
 #include "hashgrid_math.h"
+#include "hashmlp_plan.h"
 
 namespace {
 
@@ -29,8 +31,16 @@ constexpr int LDS_FLOATS = AUX_OFF + P;
 constexpr size_t LDS_BYTES = LDS_FLOATS * sizeof(float);     // 75008: two workgroups per CU
 static_assert(P * OLD <= KMAX * P, "the output tile reuses the input buffer");
 
-__device__ inline int input_width(const pixie_hashmlp_desc& m) {
-    return m.n_levels * m.features_per_level + 6 * m.n_frequencies + m.n_extra;
+static_assert(P == hmp::kTile, "hashmlp_plan.h plans for this tile");
+
+// pos[3][P] = the tile's positions as given (past the end, or without positions: 0), complete on return
+__device__ inline void load_tile_positions(const float* d_positions, int64_t tile0, int64_t n, float* pos) {
+    const int tid = threadIdx.x;
+    if (tid < 3 * P) {
+        const int p = tid / 3, a = tid - 3 * p;
+        pos[a * P + p] = (d_positions != nullptr && tile0 + p < n) ? d_positions[(tile0 + p) * 3 + a] : 0.f;
+    }
+    __syncthreads();
 }
 
 // X[column][point] of the tile's rows.  pos: LDS [3][P] unit-cube positions.
@@ -38,9 +48,7 @@ __device__ void encode_tile(const pixie_hashmlp_desc& m, const float* pos, const
     const int tid = threadIdx.x, F = m.features_per_level;
     for (int item = tid; item < m.n_levels * P; item += THREADS) {
         const int l = item >> 6, p = item & (P - 1);
-        hg::Level lv;
-        lv.scale = m.level[l].scale; lv.shift = m.level[l].shift; lv.res = m.level[l].res;
-        lv.size = m.level[l].size; lv.offset = m.level[l].offset; lv.dense = m.level[l].dense;
+        const hg::Level lv = hg::level_of(m.level[l]);
         const float pp[3] = {pos[p], pos[P + p], pos[2 * P + p]};
         const hg::Cell s = hg::cell_of(lv, pp);
         float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -241,17 +249,11 @@ int check_desc(const pixie_hashmlp_desc* m, const char* what) {
     if (m->n_levels > 0) {
         PX_REQUIRE(m->features_per_level == 2 || m->features_per_level == 4 || m->features_per_level == 8,
                    "%s: features_per_level %d is not 2, 4 or 8", what, m->features_per_level);
-        PX_REQUIRE(m->d_table != nullptr && (reinterpret_cast<uintptr_t>(m->d_table) & 15) == 0, "%s: d_table is null or not 16-byte aligned", what);
-        for (int l = 0; l < m->n_levels; ++l) {
-            const pixie_hashgrid_level& lv = m->level[l];
-            PX_REQUIRE(lv.size > 0 && (int64_t)lv.offset + (int64_t)lv.size <= m->table_rows,
-                       "%s: level %d (offset %u, size %u) does not fit the table of %lld rows", what, l, lv.offset, lv.size, (long long)m->table_rows);
-            PX_REQUIRE(std::isfinite(lv.scale) && std::isfinite(lv.shift), "%s: level %d has a non-finite scale or shift", what, l);
-        }
+        if (check_grid_table(*m, what)) return 1;
     }
     PX_REQUIRE(m->n_frequencies >= 0 && m->n_frequencies <= 8, "%s: n_frequencies %d outside 0..8", what, m->n_frequencies);
     PX_REQUIRE(m->n_extra >= 0 && m->n_extra <= PIXIE_HASHMLP_MAX_INPUT, "%s: n_extra %d outside 0..%d", what, m->n_extra, PIXIE_HASHMLP_MAX_INPUT);
-    const int width = m->n_levels * (m->n_levels > 0 ? m->features_per_level : 0) + 6 * m->n_frequencies + m->n_extra;
+    const int width = hg::input_width(*m);
     PX_REQUIRE(width >= 1 && width <= PIXIE_HASHMLP_MAX_INPUT, "%s: input row of %d columns outside 1..%d", what, width, PIXIE_HASHMLP_MAX_INPUT);
     PX_REQUIRE(m->n_hidden >= 1 && m->n_hidden <= PIXIE_HASHMLP_MAX_LAYERS - 1, "%s: %d hidden layers outside 1..%d (each 64 wide)", what, m->n_hidden,
                PIXIE_HASHMLP_MAX_LAYERS - 1);

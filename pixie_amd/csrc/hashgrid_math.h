@@ -33,6 +33,9 @@ struct Level {
     uint32_t res, size, offset, dense;
 };
 
+// a descriptor's level (pixie_hashgrid_level: the same six fields) as a Level; a template so that this header needs no pixie_hip.h
+template <class L> HG_HD Level level_of(const L& v) { return Level{v.scale, v.shift, v.res, v.size, v.offset, v.dense}; }
+
 constexpr int kMaxLevels = 16;
 constexpr uint32_t kPrimeY = 2654435761u, kPrimeZ = 805459861u;
 
@@ -109,6 +112,15 @@ HG_HD int selector(const float* p) {
     return (p[0] > 0.0f && p[0] < 1.0f && p[1] > 0.0f && p[1] < 1.0f && p[2] > 0.0f && p[2] < 1.0f) ? 1 : 0;
 }
 
+// x -> unit-cube position q (distinct from x): the affine if A is given, then the contraction or the aabb.  Returns the selector;
+// what it masks is the caller's business.
+HG_HD int unit_position(const float* A, int contraction, const float* aabb, const float* x, float* q) {
+    if (A != nullptr) affine(A, x, q);
+    else { q[0] = x[0]; q[1] = x[1]; q[2] = x[2]; }
+    if (contraction) contract_linf(q); else normalise_aabb(aabb, q);
+    return selector(q);
+}
+
 struct Cell {
     uint32_t c[3];     // floor(q), as the uint32 the corner index is formed in (negative cells wrap)
     float w[3];        // q - floor(q)
@@ -142,6 +154,9 @@ HG_HD float corner_weight(const Cell& s, int k) {
     const float wz = (k & 4) ? s.w[2] : 1.0f - s.w[2];
     return wx * wy * wz;
 }
+
+// columns of the encoded row of a network descriptor: the grid's, the frequency block's, then the extra input columns
+template <class D> HG_HD int input_width(const D& m) { return m.n_levels * m.features_per_level + 6 * m.n_frequencies + m.n_extra; }
 
 // Frequency block, tiny-cuda-nn's ordering: output j of 3 * 2 * n has dim j / (2 n), octave (j / 2) % n, phase (j % 2) pi / 2,
 // value sin(2^octave pi x + phase); the odd outputs are taken as the cosine of the same argument.

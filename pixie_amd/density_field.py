@@ -30,20 +30,19 @@ from typing import List, Mapping, Optional
 import numpy as np
 import torch
 
+from . import _hashgrid_common as common
 from . import _lib
+from ._hashgrid_common import SCRATCH_SHIFT_OFFSET, SCRATCH_STATE_OFFSET      # noqa: F401  (tests and scripts read them here)
 from ._lib import DensityFieldDesc, DensityFieldGrads, check
 from .field_query import growth_factor, nerfstudio_levels, split_tcnn_params, tcnn_levels
 
 WIDTH, MAX_HIDDEN, MAX_INPUT, MAX_POINTS = _lib.DENSITY_FIELD_WIDTH, _lib.DENSITY_FIELD_MAX_LAYERS - 1, _lib.DENSITY_FIELD_MAX_INPUT, 1 << 24
 HASH_INIT_SCALE = 0.001
-SCRATCH_SHIFT_OFFSET, SCRATCH_STATE_OFFSET = 4, 8     # bytes into the scratch: int32 shift s, int32 state (pixie_hip.h)
 
 
 def train_bytes(desc, n: int):
     """(saved_bytes, scratch_bytes) of pixie_density_field_train_bytes"""
-    saved, scratch = C.c_int64(), C.c_int64()
-    check(_lib.load().pixie_density_field_train_bytes(C.byref(desc), n, C.byref(saved), C.byref(scratch)), "pixie_density_field_train_bytes")
-    return saved.value, scratch.value
+    return common.train_bytes("pixie_density_field_train_bytes", desc, n)
 
 
 def _launch_forward(field, positions, want_raw):
@@ -85,19 +84,9 @@ class _DensityFieldFunction(torch.autograd.Function):
         if need[3]:
             grads[3] = torch.empty_like(field.table)
             g.d_table = grads[3].data_ptr()
-        n_layers = field.n_hidden + 1
-        tensors = list(field.weights) + field.bias_list()
-        for j, t in enumerate(tensors):
-            if t is not None and need[4 + j]:
-                gt = torch.empty_like(t)
-                (g.d_weight if j < n_layers else g.d_bias)[j % n_layers] = gt.data_ptr()
-                grads.append(gt)
-            else:
-                grads.append(None)
+        grads += common.bind_layer_grads(g, list(field.weights) + field.bias_list(), need[4:], field.n_hidden + 1)
         desc = field.desc()
-        _, scratch_bytes = train_bytes(desc, n)
-        scratch = torch.empty(scratch_bytes + 256, dtype=torch.uint8, device=field.device)
-        scratch = scratch[(-scratch.data_ptr()) % 256:][:scratch_bytes]
+        scratch = common.aligned_scratch(train_bytes(desc, n)[1], field.device)
         with torch.cuda.device(field.device):
             check(_lib.load().pixie_density_field_backward(C.byref(desc), positions.data_ptr(), n, d_density.data_ptr(), C.byref(g),
                                                            scratch.data_ptr(), _lib.current_stream_ptr()), "pixie_density_field_backward")
@@ -258,22 +247,15 @@ class HashMLPDensityField(torch.nn.Module):
 
     # ---- the descriptor ----
     def bias_list(self):
-        out = [None] * (self.n_hidden + 1)
-        for slot, i in enumerate(self.bias_layers):
-            out[i] = self.biases[slot]
-        return out
+        return common.bias_list(self.bias_layers, self.biases, self.n_hidden + 1)
 
     def desc(self) -> DensityFieldDesc:
         """over the parameters' own storage: it follows optimiser steps, nothing is copied"""
-        for p in self.parameters():
-            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.PixieHipError(f"HashMLPDensityField: parameters must stay contiguous float32 tensors on {self.device}")
+        common.require_device_params(self, self.device, "HashMLPDensityField")
         d = DensityFieldDesc()
         d.n_levels, d.features_per_level, d.n_hidden, d.hidden_width = len(self.levels), self.features_per_level, self.n_hidden, WIDTH
         d.contraction, d.average_init_density = int(self.contraction), self.average_init_density
-        for l, lv in enumerate(self.levels):
-            d.level[l].scale, d.level[l].shift = float(lv["scale"]), float(lv["shift"])
-            d.level[l].res, d.level[l].size, d.level[l].offset, d.level[l].dense = int(lv["res"]), int(lv["size"]), int(lv["offset"]), int(lv["dense"])
+        common.fill_levels(d, self.levels)
         d.d_table, d.table_rows = self.table.data_ptr(), int(self.table.shape[0])
         for i, (w, b) in enumerate(zip(self.weights, self.bias_list())):
             d.d_weight[i] = w.data_ptr()

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._hashgrid_common import fill_levels
 from ._lib import FieldVoxelizeDesc, HashMlpDesc, check
 
 MAX_LEVELS, MAX_HIDDEN, MAX_INPUT, MAX_OUTPUT, WIDTH = _lib.HASHMLP_MAX_LEVELS, _lib.HASHMLP_MAX_LAYERS - 1, _lib.HASHMLP_MAX_INPUT, _lib.HASHMLP_MAX_OUTPUT, 64
@@ -178,9 +179,7 @@ class HashMLP:
     def fill(self, d: HashMlpDesc) -> HashMlpDesc:
         d.n_levels, d.features_per_level = len(self.levels), self.features_per_level
         d.n_frequencies, d.n_extra, d.n_hidden, d.out_dim, d.out_activation = self.n_frequencies, self.n_extra, self.n_hidden, self.out_dim, self.out_activation
-        for l, lv in enumerate(self.levels):
-            d.level[l].scale, d.level[l].shift = float(lv["scale"]), float(lv["shift"])
-            d.level[l].res, d.level[l].size, d.level[l].offset, d.level[l].dense = int(lv["res"]), int(lv["size"]), int(lv["offset"]), int(lv["dense"])
+        fill_levels(d, self.levels)
         d.d_table = self.table.data_ptr() if self.table is not None else None
         d.table_rows = int(self.table.shape[0]) if self.table is not None else 0
         for i, (w, b) in enumerate(zip(self.weights, self.biases)):
@@ -191,28 +190,36 @@ class HashMLP:
     def desc(self) -> HashMlpDesc:
         return self.fill(HashMlpDesc())
 
+    def check_inputs(self, positions, extra, who="HashMLP", max_points=None):
+        """the checks of a call's inputs, under the name `who` (TrainableHashMLP shares them) -> (n, positions, extra), both
+        contiguous float32"""
+        given = [t for t in (positions, extra) if t is not None]
+        if not given:
+            raise ValueError(f"{who}: no input")
+        for t in given:
+            if not torch.is_tensor(t) or t.device != self.device:
+                raise _lib.PixieHipError(f"{who}: inputs must be tensors on {self.device} (no CPU fallback)")
+        n = int(given[0].shape[0])
+        if max_points is not None and n > max_points:
+            raise ValueError(f"{who}: {n} points in one call, at most 2^24")
+        if positions is not None:
+            if positions.dim() != 2 or positions.shape[1] != 3:
+                raise ValueError(f"{who}: positions must be (n, 3), got {tuple(positions.shape)}")
+            positions = positions.to(torch.float32).contiguous()
+        elif len(self.levels) or self.n_frequencies:
+            raise ValueError(f"{who}: this network needs positions")
+        if (extra is not None) != (self.n_extra > 0):
+            raise ValueError(f"{who}: extra must be given iff n_extra > 0 (n_extra = {self.n_extra})")
+        if extra is not None:
+            if tuple(extra.shape) != (n, self.n_extra):
+                raise ValueError(f"{who}: extra must be {(n, self.n_extra)}, got {tuple(extra.shape)}")
+            extra = extra.to(torch.float32).contiguous()
+        return n, positions, extra
+
     def __call__(self, positions=None, extra=None) -> torch.Tensor:
         """positions (n, 3) float32 unit-cube device tensor (None for a network without grid and frequency block), extra
         (n, n_extra) -> (n, out_dim) float32.  One launch on the current stream."""
-        given = [t for t in (positions, extra) if t is not None]
-        if not given:
-            raise ValueError("HashMLP: no input")
-        for t in given:
-            if not torch.is_tensor(t) or t.device != self.device:
-                raise _lib.PixieHipError(f"HashMLP: inputs must be tensors on {self.device} (no CPU fallback)")
-        n = int(given[0].shape[0])
-        if positions is not None:
-            if positions.dim() != 2 or positions.shape[1] != 3:
-                raise ValueError(f"HashMLP: positions must be (n, 3), got {tuple(positions.shape)}")
-            positions = positions.to(torch.float32).contiguous()
-        elif len(self.levels) or self.n_frequencies:
-            raise ValueError("HashMLP: this network needs positions")
-        if (extra is not None) != (self.n_extra > 0):
-            raise ValueError(f"HashMLP: extra must be given iff n_extra > 0 (n_extra = {self.n_extra})")
-        if extra is not None:
-            if tuple(extra.shape) != (n, self.n_extra):
-                raise ValueError(f"HashMLP: extra must be {(n, self.n_extra)}, got {tuple(extra.shape)}")
-            extra = extra.to(torch.float32).contiguous()
+        n, positions, extra = self.check_inputs(positions, extra)
         out = torch.empty((n, self.out_dim), dtype=torch.float32, device=self.device)
         lib = _lib.load()
         with torch.cuda.device(self.device):

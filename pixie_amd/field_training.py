@@ -24,18 +24,16 @@ from typing import Dict, List, Optional
 
 import torch
 
+from . import _hashgrid_common as common
 from . import _lib
+from ._hashgrid_common import SCRATCH_SHIFT_OFFSET, SCRATCH_STATE_OFFSET      # noqa: F401  (tests and scripts read them here)
 from ._lib import HashMlpGrads, check
 from .field_query import ACTIVATIONS, FeatureFieldQuery, HashMLP
-
-SCRATCH_SHIFT_OFFSET, SCRATCH_STATE_OFFSET = 4, 8     # bytes into the scratch: int32 shift s, int32 state (pixie_hip.h)
 
 
 def train_bytes(desc, n: int):
     """(saved_bytes, scratch_bytes) of pixie_hashmlp_train_bytes"""
-    saved, scratch = C.c_int64(), C.c_int64()
-    check(_lib.load().pixie_hashmlp_train_bytes(C.byref(desc), n, C.byref(saved), C.byref(scratch)), "pixie_hashmlp_train_bytes")
-    return saved.value, scratch.value
+    return common.train_bytes("pixie_hashmlp_train_bytes", desc, n)
 
 
 class _HashMlpFunction(torch.autograd.Function):
@@ -79,17 +77,9 @@ class _HashMlpFunction(torch.autograd.Function):
         if has_table and need[3]:
             grads[3] = torch.empty_like(table)
             g.d_table = grads[3].data_ptr()
-        n_layers = net.n_hidden + 1
-        for j, present in enumerate(has_layers):
-            t = tensors.pop(0) if present else None
-            if present and need[4 + j]:
-                gt = torch.empty_like(t)
-                (g.d_weight if j < n_layers else g.d_bias)[j % n_layers] = gt.data_ptr()
-                grads.append(gt)
-            else:
-                grads.append(None)
-        scratch = torch.empty(ctx.scratch_bytes + 256, dtype=torch.uint8, device=dev)
-        scratch = scratch[(-scratch.data_ptr()) % 256:][:ctx.scratch_bytes]
+        layers = [tensors.pop(0) if present else None for present in has_layers]
+        grads += common.bind_layer_grads(g, layers, need[4:], net.n_hidden + 1)
+        scratch = common.aligned_scratch(ctx.scratch_bytes, dev)
         with torch.cuda.device(dev):
             check(_lib.load().pixie_hashmlp_backward(C.byref(net.desc()), positions.data_ptr() if positions is not None else None,
                                                      extra.data_ptr() if extra is not None else None, n, out.data_ptr(), saved.data_ptr(),
@@ -125,16 +115,11 @@ class TrainableHashMLP(torch.nn.Module):
         return self
 
     def bias_list(self):
-        out = [None] * (self.n_hidden + 1)
-        for slot, i in enumerate(self.bias_layers):
-            out[i] = self.biases[slot]
-        return out
+        return common.bias_list(self.bias_layers, self.biases, self.n_hidden + 1)
 
     def to_hashmlp(self) -> HashMLP:
         """a HashMLP over the parameters' storage (it follows optimiser steps; nothing is copied)"""
-        for p in self.parameters():
-            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.PixieHipError(f"TrainableHashMLP: parameters must stay contiguous float32 tensors on {self.device}")
+        common.require_device_params(self, self.device, "TrainableHashMLP")
         return HashMLP(self.levels if len(self.levels) else None, self.table, list(self.weights), self.bias_list(), self.n_frequencies, self.n_extra,
                        self.out_activation, self.device)
 
@@ -146,27 +131,7 @@ class TrainableHashMLP(torch.nn.Module):
         wants = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or (torch.is_tensor(extra) and extra.requires_grad))
         if not wants:
             return net(positions, extra)
-        given = [t for t in (positions, extra) if t is not None]
-        if not given:
-            raise ValueError("TrainableHashMLP: no input")
-        for t in given:
-            if not torch.is_tensor(t) or t.device != self.device:
-                raise _lib.PixieHipError(f"TrainableHashMLP: inputs must be tensors on {self.device} (no CPU fallback)")
-        n = int(given[0].shape[0])
-        if n > 1 << 24:
-            raise ValueError(f"TrainableHashMLP: {n} points in one call, at most 2^24")
-        if positions is not None:
-            if positions.dim() != 2 or positions.shape[1] != 3:
-                raise ValueError(f"TrainableHashMLP: positions must be (n, 3), got {tuple(positions.shape)}")
-            positions = positions.to(torch.float32).contiguous()
-        elif len(self.levels) or self.n_frequencies:
-            raise ValueError("TrainableHashMLP: this network needs positions")
-        if (extra is not None) != (self.n_extra > 0):
-            raise ValueError(f"TrainableHashMLP: extra must be given iff n_extra > 0 (n_extra = {self.n_extra})")
-        if extra is not None:
-            if tuple(extra.shape) != (n, self.n_extra):
-                raise ValueError(f"TrainableHashMLP: extra must be {(n, self.n_extra)}, got {tuple(extra.shape)}")
-            extra = extra.to(torch.float32).contiguous()
+        _, positions, extra = net.check_inputs(positions, extra, "TrainableHashMLP", 1 << 24)
         return _HashMlpFunction.apply(net, positions, extra, self.table, *self.weights, *self.bias_list())
 
 

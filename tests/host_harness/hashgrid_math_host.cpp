@@ -35,6 +35,11 @@ void hh_hg_unit(const float* A, int contraction, const float* aabb, const float*
     }
 }
 
+// the same through hg::unit_position, the function the kernels call; A may be null (no affine)
+void hh_hg_unit_position(const float* A, int contraction, const float* aabb, const float* x, int64_t n, float* p, int32_t* sel) {
+    for (int64_t i = 0; i < n; ++i) sel[i] = hg::unit_position(A, contraction, aabb, x + 3 * i, p + 3 * i);
+}
+
 // rows (n, 8) and weights (n, 8) of one level
 void hh_hg_corners(const hg::Level* lv, const float* p, int64_t n, uint32_t* rows, float* weights) {
     for (int64_t i = 0; i < n; ++i) {
@@ -97,6 +102,10 @@ int main() {
     for (auto& v : x) v = 6.f * rnd() - 3.f;
     hh_hg_unit(A, 1, aabb, x.data(), 512, q.data(), sel.data());
     hh_hg_unit(A, 0, aabb, x.data(), 512, q.data(), sel.data());
+    for (int contraction = 0; contraction < 2; ++contraction) {
+        hh_hg_unit_position(A, contraction, aabb, x.data(), 512, q.data(), sel.data());
+        hh_hg_unit_position(nullptr, contraction, aabb, x.data(), 512, q.data(), sel.data());
+    }
     printf("checksum %.6f\nok\n", sum);
     return 0;
 }

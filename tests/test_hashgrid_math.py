@@ -31,6 +31,7 @@ def host(tmp_path_factory):
     h.hh_hg_levels.argtypes = [C.c_int] * 5 + [C.POINTER(_lib.HashGridLevel), C.POINTER(C.c_int64)]
     h.hh_hg_lattice.argtypes = [C.c_double, C.c_double, C.c_int, FP]
     h.hh_hg_unit.argtypes = [FP, C.c_int, FP, FP, C.c_int64, FP, I32]
+    h.hh_hg_unit_position.argtypes = [FP, C.c_int, FP, FP, C.c_int64, FP, I32]
     h.hh_hg_corners.argtypes = [C.POINTER(_lib.HashGridLevel), FP, C.c_int64, U32, FP]
     h.hh_hg_encode.argtypes = [C.POINTER(_lib.HashGridLevel), C.c_int, FP, C.c_int, FP, C.c_int64, FP]
     h.hh_hg_frequency_args.argtypes = [FP, C.c_int64, C.c_int, FP]
@@ -123,6 +124,21 @@ def test_unit_positions_and_selector_equal_the_restatement(host, contraction):
         assert np.array_equal(p.view(np.uint32), want_p.view(np.uint32))
         assert np.array_equal(sel.astype(bool), want_sel)
         assert sel.all() if contraction else 0 < sel.sum() < len(x)      # every finite point contracts to the inside of the cube
+    # hg::unit_position itself, the function the kernels call: with the affine, and without one (null), where the restatement's
+    # identity affine is exact for finite coordinates
+    x[5:8] = [[np.nan, 0.25, 0.5], [-1, 1, -1], [3, 0.5, 2.5]]                  # a NaN coordinate, |x|_inf exactly 1, a point outside
+    finite = np.arange(len(x)) != 5
+    for M in (None, A):
+        p, sel = np.zeros_like(x), np.zeros(len(x), np.int32)
+        host.hh_hg_unit_position(fp(M) if M is not None else None, int(contraction), fp(aabb), fp(x), len(x), fp(p), sel.ctypes.data_as(I32))
+        want_p, want_sel = R.world_to_unit(x[finite], np.eye(4, dtype=np.float32)[:3] if M is None else M, contraction, aabb)
+        assert np.array_equal(p[finite].view(np.uint32), want_p.view(np.uint32))
+        assert np.array_equal(sel[finite].astype(bool), want_sel)
+        assert sel[5] == 0 and np.isnan(p[5, 0]), "a NaN coordinate stays NaN and selects nothing"
+        assert sel[7] == int(contraction), "a point outside: contracted into the cube, or left outside the aabb"
+        if M is None:
+            want6 = [0.25, 0.75, 0.25] if contraction else [0, 1, 0]           # the far branch of the contraction is the identity at 1
+            assert np.array_equal(p[6], np.float32(want6)) and sel[6] == int(contraction)
 
 
 @pytest.mark.parametrize("convention", ["nerfstudio", "tcnn"])
